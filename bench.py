@@ -3,6 +3,7 @@
 with p50 TTFT, sharded PP=N across N MI355X GPUs (BASELINE.json metric).
 
 Single GPU:      python bench.py --steps 3 --warmup 1
+Compare builds:  python bench.py --steps 3 --warmup 1 --dump-outputs DIR
 Multi GPU (driver): python -m torch.distributed.run --nnodes=1 \
     --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
@@ -11,6 +12,13 @@ A "step" is one full serving round: prefill a synthetic batch of prompts
 decode a fixed number of new tokens per sequence. Weak scaling: the per-GPU
 batch is fixed, so the global batch grows with N. Rank 0 prints ONE JSON
 line with the aggregate output tokens/sec over the whole job.
+
+A plain run only sets up, warms up, times the steps and prints that line.
+--dump-outputs DIR also writes what the last timed step returned to its
+caller as DIR/<name>.npy; weights, prompts and greedy decoding are seeded,
+so two builds run with the same arguments can be compared array for array.
+--full is where any measurement beyond the headline figure belongs (none
+today: the TTFT in the result line falls out of the timed steps).
 """
 
 import argparse
@@ -20,11 +28,13 @@ import statistics
 import sys
 import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from tensorlink_amd.models.configs import get_config  # noqa: E402
+from tensorlink_amd.models.loader import skip_default_init  # noqa: E402
 from tensorlink_amd.parallel.comm import init_distributed  # noqa: E402
 from tensorlink_amd.parallel.planner import plan_for_world  # noqa: E402
 from tensorlink_amd.parallel.pipeline import (  # noqa: E402
@@ -46,7 +56,33 @@ def parse_args():
     p.add_argument("--mode", choices=["serve", "train"], default="serve")
     p.add_argument("--dp", type=int, default=1,
                    help="data-parallel replicas (train mode; world=dp*pp)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs as "
+                        "DIR/<name>.npy (float64)")
+    p.add_argument("--full", action="store_true",
+                   help="also run every measurement beyond the headline "
+                        "figure (none today)")
     return p.parse_args()
+
+
+DUMP_LIMIT_BYTES = 60_000_000       # array data; headers stay under 64 MB
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: array-like} as out_dir/<name>.npy in float64, at most
+    DUMP_LIMIT_BYTES in all: a larger array is cut down to a fixed, seeded
+    sample of its flattened elements (same indices every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // 8 // max(1, len(arrays))
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().to("cpu", torch.float64).numpy()
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > budget:
+            idx = np.random.default_rng(0).choice(a.size, budget,
+                                                  replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def run_train(args, rank, world, device, use_gpu, config):
@@ -80,6 +116,9 @@ def run_train(args, rank, world, device, use_gpu, config):
         e = torch.tensor([elapsed], dtype=torch.float64)
         torch.distributed.all_reduce(e, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(e.item())
+    if rank == 0 and args.dump_outputs:
+        # train_step hands its caller the step's loss and nothing else
+        dump_outputs(args.dump_outputs, {"loss": [losses[-1]]})
     if rank == 0:
         print(json.dumps({
             "metric": "training tokens/sec (1F1B pipeline + fused AdamW)",
@@ -123,8 +162,12 @@ def main():
     B = args.batch_per_gpu * world          # weak scaling: global batch
     S, T = args.prompt_len, args.new_tokens
     plan = plan_for_world(config, world, batch_size=B, seq_len=S + T)
-    runner = PipelineRunner(plan, rank, world, device=device, init="random",
-                            seed=1234)
+    # the seeded random init below overwrites every weight, and the host
+    # RNG is re-seeded before the prompts are drawn: skip torch's default
+    # init, which costs most of a minute of host time on the 7B model
+    with skip_default_init():
+        runner = PipelineRunner(plan, rank, world, device=device,
+                                init="random", seed=1234)
 
     torch.manual_seed(17)
     input_ids = torch.randint(0, config.vocab_size, (B, S)) \
@@ -146,11 +189,12 @@ def main():
         runner.generate(input_ids, sp, micro_batches=n_mb)
 
     ttfts = []
+    out = None
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        _, stats = runner.generate(input_ids, sp, micro_batches=n_mb,
-                                   return_stats=True)
+        out, stats = runner.generate(input_ids, sp, micro_batches=n_mb,
+                                     return_stats=True)
         if rank == 0:
             print(f"[step] {stats}", file=sys.stderr)
         tt = stats.get("ttft_p50_s", stats.get("ttft_s"))
@@ -179,6 +223,10 @@ def main():
     if os.environ.get("TL_TRACE"):          # per-rank Chrome trace export
         from tensorlink_amd.utils.tracing import export_from_env
         export_from_env(runner.tracer)
+
+    if rank == 0 and args.dump_outputs:
+        # generate() returns the new token ids [B, T] on rank 0
+        dump_outputs(args.dump_outputs, {"tokens": out})
 
     if rank == 0:
         print(json.dumps({

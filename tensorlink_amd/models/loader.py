@@ -12,6 +12,7 @@ bench.py / smoke (BASELINE.json: "synthetic data / random-init weights").
 
 from __future__ import annotations
 
+import contextlib
 import json
 import math
 import os
@@ -155,6 +156,27 @@ def load_stage_from_checkpoint(stage: StageModel, ckpt_dir: str,
                 loaded += 1
     stage.to(device=device, dtype=dtype)
     return loaded
+
+
+@contextlib.contextmanager
+def skip_default_init():
+    """Build modules without torch's default weight init.
+
+    nn.Linear / nn.Embedding draw every weight on the host in their
+    constructors (most of a minute for a 7B stage) and
+    `init_random_stage` overwrites every one of those values afterwards.
+    Inside this context the constructors leave the weights uninitialized.
+    The host RNG is then not advanced by construction, so this is opt-in
+    for callers that seed it themselves afterwards (bench.py)."""
+    saved = [(cls, cls.reset_parameters)
+             for cls in (torch.nn.Linear, torch.nn.Embedding)]
+    for cls, _ in saved:
+        cls.reset_parameters = lambda self: None
+    try:
+        yield
+    finally:
+        for cls, fn in saved:
+            cls.reset_parameters = fn
 
 
 @torch.no_grad()
