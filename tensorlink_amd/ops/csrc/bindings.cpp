@@ -22,7 +22,7 @@ void tl_swiglu_fwd(const void* gate, const void* up, void* out, int64_t n,
 void tl_swiglu_bwd(const void* dout, const void* gate, const void* up,
                    void* dgate, void* dup, int64_t n, hipStream_t stream);
 void tl_adamw(void* param, const void* grad, void* m, void* v, int64_t n,
-              int is_bf16, float lr, float beta1, float beta2, float eps,
+              int is_bf16, float lr, double beta1, double beta2, float eps,
               float weight_decay, int step, hipStream_t stream);
 void tl_decode_attn(const void* q, const void* k_cache, const void* v_cache,
                     const void* seq_lens, void* out, int B, int Hq, int Hkv,
@@ -95,6 +95,7 @@ std::vector<Tensor> rmsnorm_fwd(Tensor x, c10::optional<Tensor> residual,
   CHECK_IN(w, torch::kBFloat16);
   const int H = x.size(-1);
   TORCH_CHECK(H % 8 == 0, "H must be divisible by 8");
+  TORCH_CHECK(H <= 16384, "rmsnorm supports H <= 16384");
   const int64_t N = x.numel() / H;
   auto y = torch::empty_like(x);
   Tensor rstd, r_out;
@@ -122,6 +123,8 @@ std::vector<Tensor> rmsnorm_bwd(Tensor dy, Tensor x, Tensor w, Tensor rstd) {
   CHECK_IN(w, torch::kBFloat16);
   CHECK_IN(rstd, torch::kFloat);
   const int H = x.size(-1);
+  TORCH_CHECK(H % 8 == 0, "H must be divisible by 8");
+  TORCH_CHECK(H <= 16384, "rmsnorm supports H <= 16384");
   const int64_t N = x.numel() / H;
   const int n_blocks = (int)std::min<int64_t>(N, 512);
   auto dx = torch::empty_like(x);
@@ -179,8 +182,8 @@ void adamw_(Tensor param, Tensor grad, Tensor m, Tensor v, double lr,
   const bool is_bf16 = param.scalar_type() == torch::kBFloat16;
   TORCH_CHECK(is_bf16 || param.scalar_type() == torch::kFloat);
   tl_adamw(param.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(),
-           param.numel(), is_bf16 ? 1 : 0, (float)lr, (float)beta1,
-           (float)beta2, (float)eps, (float)weight_decay, (int)step,
+           param.numel(), is_bf16 ? 1 : 0, (float)lr, beta1, beta2,
+           (float)eps, (float)weight_decay, (int)step,
            cur_stream());
 }
 

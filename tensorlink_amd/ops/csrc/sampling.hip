@@ -11,11 +11,14 @@
 //     matching torch.argmax).
 //   sampled: pass 1 finds the penalized max M; pass 2 builds a 256-bin
 //     histogram over the top 8 bits of the ORDERED float key of z
-//     (count + sum of exp((z-M)/T) per bin, LDS atomics); the top-k /
-//     top-p cutoff bin is refined with a second 8-bit level — exact for
+//     (count + sum of exp((z-M)/T) per bin, LDS atomics); the top-k
+//     cutoff bin is refined with a second 8-bit level — exact for
 //     bf16-sourced values (bf16 = top 16 f32 bits) — giving a value
-//     threshold t and the kept probability mass S; pass 4 walks the row
-//     in index order accumulating kept weights until u*S is crossed.
+//     threshold; pass 3 does the same for top-p over the tokens that
+//     survive the k cut (p mass of the SURVIVORS, as the torch
+//     reference renormalises after top-k), giving the final threshold t
+//     and the kept probability mass S; pass 4 walks the row in index
+//     order accumulating kept weights until u*S is crossed.
 //   Ties at the threshold are all kept (the torch reference cuts ties
 //   in sort order at exactly-k / crossing-p; including value-ties only
 //   ever adds tokens of identical probability).
@@ -64,8 +67,7 @@ struct SampleLds {
     BlockRed red;
     float scan[BLOCK / 64];
   } u;
-  float stat[8];        // float broadcast slots
-  unsigned long long statu[4];   // integer broadcast slots
+  unsigned long long statu[4];   // broadcast slots (bins, counts, masses)
 };
 
 DEVINLINE unsigned long long wquant(float e) {
@@ -160,68 +162,15 @@ __global__ __launch_bounds__(BLOCK) void sample_kernel(
     const float invT = 1.f / T;
     const int k_want = top_ks[b];
     const float p_want = top_ps[b];
-    // -------- pass 2: level-1 histogram (key bits 31:24) --------
-    for (int i = tid; i < 256; i += BLOCK) {
-      lds.u.hist.cnt[i] = 0;
-      lds.u.hist.sum[i] = 0ull;
-    }
-    __syncthreads();
-    for (int i = tid; i < V; i += BLOCK) {
-      float z = zval(i);
-      float e = __expf((z - M) * invT);
-      uint32_t bin = fkey(z) >> 24;
-      atomicAdd(&lds.u.hist.cnt[bin], 1);
-      atomicAdd(&lds.u.hist.sum[bin], wquant(e));
-    }
-    __syncthreads();
-    // walk bins high->low on ONE thread (256 iterations, trivial)
-    if (tid == 0) {
-      unsigned long long Zi = 0ull;
-      for (int i = 0; i < 256; ++i) Zi += lds.u.hist.sum[i];
-      const unsigned long long pmass =
-          p_want < 1.f ? (unsigned long long)(p_want * (double)Zi)
-                       : ~0ull;
-      long cum_n = 0;
-      unsigned long long cum_e = 0ull;
-      int bin_k = -1, bin_p = -1;     // boundary bins
-      long above_k = 0;               // counts/mass strictly above bin
-      unsigned long long above_p = 0ull;
-      for (int i = 255; i >= 0; --i) {
-        if (bin_k < 0 && k_want > 0 &&
-            cum_n + lds.u.hist.cnt[i] >= k_want) {
-          bin_k = i; above_k = cum_n;
-        }
-        if (bin_p < 0 && cum_e + lds.u.hist.sum[i] > pmass) {
-          bin_p = i; above_p = cum_e;
-        }
-        cum_n += lds.u.hist.cnt[i];
-        cum_e += lds.u.hist.sum[i];
-        if (bin_k >= 0 && bin_p >= 0) break;
-      }
-      if (k_want <= 0 || k_want >= V) bin_k = 0;       // no k cut
-      if (bin_k < 0) bin_k = 0;
-      if (bin_p < 0) bin_p = 0;                        // no p cut
-      lds.stat[1] = (float)bin_k;
-      lds.stat[2] = (float)bin_p;
-      lds.stat[3] = (float)above_k;   // exact up to 2^24 counts
-      lds.statu[0] = above_p;
-      lds.statu[1] = pmass;
-    }
-    __syncthreads();
-    const int bin_k = (int)lds.stat[1];
-    const int bin_p = (int)lds.stat[2];
-    const unsigned long long pmass = lds.statu[1];
-
-    // -------- pass 3: level-2 refinement for both cutoffs --------
-    // elements whose level-1 bin == boundary get re-binned by key bits
-    // 23:16; run for k and p boundaries (they often coincide)
+    const bool use_k = k_want > 0 && k_want < V;
+    const bool use_p = p_want < 1.f;
     uint32_t thr_key = 0;        // keep keys >= thr_key
     float kept_mass = -1.f;      // computed below (full Z if no cuts)
-    for (int phase = 0; phase < 2; ++phase) {
-      const bool is_k = phase == 0;
-      if (is_k && (k_want <= 0 || k_want >= V)) continue;
-      if (!is_k && !(top_ps[b] < 1.f)) continue;
-      const int bb = is_k ? bin_k : bin_p;
+
+    // Histogram over the elements with key >= min_key: bb < 0 bins the
+    // whole row by key bits 31:24 (level 1); bb >= 0 re-bins the
+    // elements of level-1 bin bb by key bits 23:16 (level 2).
+    auto build_hist = [&](int bb, uint32_t min_key) {
       for (int i = tid; i < 256; i += BLOCK) {
         lds.u.hist.cnt[i] = 0;
         lds.u.hist.sum[i] = 0ull;
@@ -230,37 +179,86 @@ __global__ __launch_bounds__(BLOCK) void sample_kernel(
       for (int i = tid; i < V; i += BLOCK) {
         float z = zval(i);
         uint32_t key = fkey(z);
-        if ((int)(key >> 24) == bb) {
-          float e = __expf((z - M) * invT);
-          atomicAdd(&lds.u.hist.cnt[(key >> 16) & 0xFF], 1);
-          atomicAdd(&lds.u.hist.sum[(key >> 16) & 0xFF], wquant(e));
-        }
+        if (key < min_key) continue;
+        if (bb >= 0 && (int)(key >> 24) != bb) continue;
+        float e = __expf((z - M) * invT);
+        uint32_t bin = bb < 0 ? (key >> 24) : ((key >> 16) & 0xFF);
+        atomicAdd(&lds.u.hist.cnt[bin], 1);
+        atomicAdd(&lds.u.hist.sum[bin], wquant(e));
       }
       __syncthreads();
+    };
+
+    // -------- pass 2: top-k value threshold (two 8-bit levels) --------
+    // bins are walked high->low on ONE thread (256 iterations, trivial)
+    if (use_k) {
+      build_hist(-1, 0u);
       if (tid == 0) {
-        long cum_n = (long)lds.stat[3];
-        unsigned long long cum_e = lds.statu[0];
-        int sub = 0;
-        if (is_k) {
-          for (int i = 255; i >= 0; --i) {
-            cum_n += lds.u.hist.cnt[i];
-            if (cum_n >= k_want) { sub = i; break; }
-          }
-        } else {
-          for (int i = 255; i >= 0; --i) {
-            cum_e += lds.u.hist.sum[i];
-            if (cum_e > pmass) { sub = i; break; }
-          }
+        long cum_n = 0;
+        int bin = 0;
+        for (int i = 255; i >= 0; --i) {
+          if (cum_n + lds.u.hist.cnt[i] >= k_want) { bin = i; break; }
+          cum_n += lds.u.hist.cnt[i];
         }
-        // keep keys >= boundary sub-bin start
-        lds.stat[6] = (float)sub;
-        lds.stat[7] = __uint_as_float(
-            ((uint32_t)bb << 24) | ((uint32_t)sub << 16));
+        lds.statu[0] = (unsigned long long)bin;
+        lds.statu[1] = (unsigned long long)cum_n;   // count above the bin
       }
       __syncthreads();
-      uint32_t t = __float_as_uint(lds.stat[7]);
-      if (t > thr_key) thr_key = t;
+      const int bin_k = (int)lds.statu[0];
+      build_hist(bin_k, 0u);
+      if (tid == 0) {
+        long cum_n = (long)lds.statu[1];
+        int sub = 0;
+        for (int i = 255; i >= 0; --i) {
+          cum_n += lds.u.hist.cnt[i];
+          if (cum_n >= k_want) { sub = i; break; }
+        }
+        lds.statu[2] = ((unsigned long long)bin_k << 24) |
+                       ((unsigned long long)sub << 16);
+      }
       __syncthreads();
+      thr_key = (uint32_t)lds.statu[2];
+    }
+
+    // -------- pass 3: top-p threshold over the top-k SURVIVORS --------
+    // the k cut is settled first and the p mass is taken over the keys
+    // that survive it (ops/reference.py sample_token: mask to the top k,
+    // then top-p on the renormalised rest). With no k cut thr_key is 0
+    // and the histograms cover the whole row.
+    if (use_p) {
+      build_hist(-1, thr_key);
+      if (tid == 0) {
+        unsigned long long Zi = 0ull;
+        for (int i = 0; i < 256; ++i) Zi += lds.u.hist.sum[i];
+        const unsigned long long pmass =
+            (unsigned long long)(p_want * (double)Zi);
+        unsigned long long cum_e = 0ull;
+        int bin = 0;
+        for (int i = 255; i >= 0; --i) {
+          if (cum_e + lds.u.hist.sum[i] > pmass) { bin = i; break; }
+          cum_e += lds.u.hist.sum[i];
+        }
+        lds.statu[0] = (unsigned long long)bin;
+        lds.statu[1] = cum_e;                       // mass above the bin
+        lds.statu[3] = pmass;
+      }
+      __syncthreads();
+      const int bin_p = (int)lds.statu[0];
+      build_hist(bin_p, thr_key);
+      if (tid == 0) {
+        unsigned long long cum_e = lds.statu[1];
+        const unsigned long long pmass = lds.statu[3];
+        int sub = 0;
+        for (int i = 255; i >= 0; --i) {
+          cum_e += lds.u.hist.sum[i];
+          if (cum_e > pmass) { sub = i; break; }
+        }
+        lds.statu[2] = ((unsigned long long)bin_p << 24) |
+                       ((unsigned long long)sub << 16);
+      }
+      __syncthreads();
+      const uint32_t t = (uint32_t)lds.statu[2];
+      if (t > thr_key) thr_key = t;
     }
     // kept mass for the final threshold (fixed-order float pass)
     {
