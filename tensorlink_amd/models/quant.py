@@ -154,17 +154,20 @@ def quantize_dense_fp8(stage: nn.Module) -> int:
 # ---------------------------------------------------------------------------
 # MXFP4 (OCP microscaling fp4): the gfx950-native 4-bit format
 # ---------------------------------------------------------------------------
-_E2M1_VALUES = torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0])
+# the dequantizer lives with the op reference (ops.mxfp4_linear's CPU
+# path) and is re-exported here, its public home
+from tensorlink_amd.ops.reference import (  # noqa: E402,F401
+    _E2M1_VALUES, dequantize_mxfp4)
 
 
 def quantize_mxfp4(w: torch.Tensor, group: int = 32):
     """Quantize [N, K] weights to MXFP4: groups of 32 along K share one
     power-of-two e8m0 scale; elements are e2m1 (±{0,.5,1,1.5,2,3,4,6}),
-    packed two per byte. This is the exact operand format of gfx950's
-    scaled-MFMA instructions (CDNA4 guide §MX), so round-2's 4-bit GEMM
-    kernel consumes these tensors directly; until then Fp4Linear
-    dequantizes on the fly. Returns (packed [N, K//2] uint8,
-    exponents [N, K/group] int8)."""
+    packed two per byte: element 2i in the low nibble, 2i+1 in the high
+    nibble. ops/csrc/mxfp4_gemm.hip consumes these tensors directly
+    (weight-only: bf16 activations, in-register expansion to bf16).
+    Returns (packed [N, K//2] uint8, exponents [N, K/group] int8,
+    unbiased powers of two)."""
     N, K = w.shape
     assert K % group == 0
     wf = w.float().reshape(N, K // group, group)
@@ -181,25 +184,13 @@ def quantize_mxfp4(w: torch.Tensor, group: int = 32):
     return packed, e.to(torch.int8)
 
 
-def dequantize_mxfp4(packed: torch.Tensor, exponents: torch.Tensor,
-                     group: int = 32, dtype=torch.float32):
-    N = packed.shape[0]
-    K = packed.shape[1] * 2
-    code = torch.empty(N, K, dtype=torch.uint8, device=packed.device)
-    code[:, 0::2] = packed & 0xF
-    code[:, 1::2] = packed >> 4
-    vals = _E2M1_VALUES.to(packed.device)
-    mag = vals[(code & 0x7).long()]
-    sign = torch.where((code & 0x8) != 0, -1.0, 1.0)
-    scale = torch.pow(2.0, exponents.float()).repeat_interleave(group, -1)
-    return (mag * sign * scale).to(dtype)
-
-
 class Fp4Linear(nn.Module):
     """Weight-only MXFP4 linear: 4x smaller weights than bf16. Forward
-    dequantizes per call (correct everywhere; the scaled-MFMA GEMM that
-    consumes the packed form directly is round-2 kernel work —
-    ROADMAP.md §6)."""
+    goes through ops.mxfp4_linear: on GPU the packed weights feed the
+    hand-written GEMM (ops/csrc/mxfp4_gemm.hip, hipGraph-capturable, no
+    dequantized copy is kept); on CPU the fp32 reference dequantizes per
+    call. The scaled-MFMA variant for compute-bound M is open work
+    (ROADMAP.md §6)."""
 
     def __init__(self, packed, exponents, bias, in_features, out_features):
         super().__init__()
@@ -215,11 +206,8 @@ class Fp4Linear(nn.Module):
         return cls(packed, e, lin.bias, lin.in_features, lin.out_features)
 
     def forward(self, x):
-        w = dequantize_mxfp4(self.packed, self.exponents, dtype=torch.float32)
-        y = torch.nn.functional.linear(x.float(), w,
-                                       self.bias.float()
-                                       if self.bias is not None else None)
-        return y.to(x.dtype)
+        from tensorlink_amd import ops
+        return ops.mxfp4_linear(x, self.packed, self.exponents, self.bias)
 
 
 def quantize_dense_fp4(stage: nn.Module) -> int:

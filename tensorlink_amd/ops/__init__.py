@@ -390,6 +390,49 @@ def linear(x: torch.Tensor, weight: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# MXFP4 weight-only linear
+# ---------------------------------------------------------------------------
+# incremented whenever mxfp4_gemm.hip handles a linear (same purpose as
+# gemm_dispatch_count: a silent fallback cannot pass as kernel coverage)
+mxfp4_dispatch_count = 0
+
+
+def _use_mxfp4_gemm(M: int, N: int, K: int) -> bool:
+    # 512 is the binding's own row limit: a raised TL_GEMM_M_MAX must
+    # not turn into an error there
+    return (N > 0 and N % 64 == 0 and K > 0 and K % 128 == 0
+            and 1 <= M <= min(GEMM_M_MAX, 512))
+
+
+def mxfp4_linear(x: torch.Tensor, packed: torch.Tensor,
+                 exponents: torch.Tensor,
+                 bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x @ dequant(packed, exponents)^T + bias for MXFP4 weights as
+    models.quant.quantize_mxfp4 emits them (packed [N, K/2] uint8,
+    exponents [N, K/32] int8). GPU bf16 rows at serving M run the
+    hand-written weight-only kernel (ops/csrc/mxfp4_gemm.hip): bitwise
+    M-independent rows, hipGraph-capturable, no dequantized copy. Other
+    GPU inputs dequantize once to bf16 (exact) and use F.linear; CPU runs
+    the fp32 reference."""
+    global mxfp4_dispatch_count
+    if not _on_gpu(x):
+        return ref.mxfp4_linear(x, packed, exponents, bias)
+    K = x.shape[-1]
+    M = x.numel() // K if K else 0
+    N = packed.shape[0]
+    if (x.dtype == torch.bfloat16 and _C is not None
+            and _use_mxfp4_gemm(M, N, K)):
+        mxfp4_dispatch_count += 1
+        return _C.mxfp4_gemm(
+            x.contiguous(), packed.contiguous(), exponents.contiguous(),
+            bias.to(torch.bfloat16).contiguous()
+            if bias is not None else None)
+    w = ref.dequantize_mxfp4(packed, exponents, dtype=torch.bfloat16)
+    return torch.nn.functional.linear(
+        x, w.to(x.dtype), bias.to(x.dtype) if bias is not None else None)
+
+
+# ---------------------------------------------------------------------------
 # AdamW
 # ---------------------------------------------------------------------------
 def adamw_(param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor,

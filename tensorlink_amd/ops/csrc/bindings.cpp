@@ -57,6 +57,9 @@ void tl_bump_counter(void* ctr, hipStream_t stream);
 void tl_moe_gemm(const void* x, const void* tok_idx, const void* seg_off,
                  const void* w_ptrs, const void* s_ptrs, void* out, int E,
                  int N, int K, int fp8, hipStream_t stream);
+void tl_mxfp4_gemm(const void* x, const void* packed, const void* exps,
+                   const void* bias, void* out, void* partial, int M, int N,
+                   int K, int n_split, hipStream_t stream);
 void tl_prefill_attn_lse(const void* q, const void* k, const void* v,
                          void* out, void* lse, int B, int Sq, int Skv,
                          int q_off, int Hq, int Hkv, int D, float scale,
@@ -418,6 +421,66 @@ Tensor skinny_gemm(Tensor x, Tensor w, c10::optional<Tensor> bias) {
   return out;
 }
 
+// Split-K policy of the MXFP4 weight GEMM (mxfp4_gemm.hip). (N,K)-pure like
+// gemm_n_split, but counted in the kernel's 128-k steps: a column's packed
+// bytes are 4x fewer than bf16, so a split must keep >= 2 steps.
+static int mxfp4_n_split(int N, int K) {
+  int n_split = 1;
+  while ((N / 64) * n_split < 256 && n_split < 8 &&
+         (K / 128) / (n_split * 2) >= 2)
+    n_split <<= 1;
+  return n_split;
+}
+
+int64_t mxfp4_n_split_py(int64_t N, int64_t K) {
+  TORCH_CHECK(N > 0 && K > 0 && N % 64 == 0 && K % 128 == 0,
+              "unsupported shape");
+  return mxfp4_n_split((int)N, (int)K);
+}
+
+Tensor mxfp4_gemm(Tensor x, Tensor packed, Tensor exponents,
+                  c10::optional<Tensor> bias) {
+  CHECK_IN(x, torch::kBFloat16);
+  CHECK_IN(packed, torch::kByte);
+  CHECK_IN(exponents, torch::kChar);
+  TORCH_CHECK(packed.dim() == 2 && exponents.dim() == 2,
+              "packed / exponents must be 2-D");
+  TORCH_CHECK(x.dim() >= 1, "x must have a K dimension");
+  const int64_t K = x.size(-1);
+  const int64_t N = packed.size(0);
+  TORCH_CHECK(K > 0 && N > 0 && N % 64 == 0 && K % 128 == 0,
+              "unsupported shape: need N % 64 == 0 and K % 128 == 0");
+  TORCH_CHECK(packed.size(1) * 2 == K, "packed must be [N, K/2]");
+  TORCH_CHECK(exponents.size(0) == N && exponents.size(1) * 32 == K,
+              "exponents must be [N, K/32]");
+  const int64_t M = x.numel() / K;
+  TORCH_CHECK(M >= 1 && M <= 512, "mxfp4_gemm supports 1 <= M <= 512");
+  TORCH_CHECK(packed.device() == x.device() &&
+                  exponents.device() == x.device(),
+              "operands must share a device");
+  auto sizes = x.sizes().vec();
+  sizes.back() = N;
+  auto out = torch::empty(sizes, x.options());
+  const void* bp = nullptr;
+  if (bias.has_value()) {
+    CHECK_IN(bias.value(), torch::kBFloat16);
+    TORCH_CHECK(bias->numel() == N, "bias must be [N]");
+    bp = bias->data_ptr();
+  }
+  const int n_split = mxfp4_n_split((int)N, (int)K);
+  Tensor partial;
+  void* pp = nullptr;
+  if (n_split > 1) {
+    partial = torch::empty({(int64_t)n_split * M * N},
+                           x.options().dtype(torch::kFloat));
+    pp = partial.data_ptr();
+  }
+  tl_mxfp4_gemm(x.data_ptr(), packed.data_ptr(), exponents.data_ptr(), bp,
+                out.data_ptr(), pp, (int)M, (int)N, (int)K, n_split,
+                cur_stream());
+  return out;
+}
+
 Tensor sample_tokens(Tensor logits, Tensor temps, Tensor top_ps,
                      Tensor top_ks, Tensor pres, Tensor freqs,
                      c10::optional<Tensor> counts,
@@ -512,6 +575,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "advance the graph-safe sampling RNG counter");
   mod.def("moe_gemm", &moe_gemm,
           "grouped expert GEMM over expert-sorted pair rows");
+  mod.def("mxfp4_gemm", &mxfp4_gemm,
+          "weight-only MXFP4 GEMM: x @ dequant(packed, exponents)^T + bias");
+  mod.def("mxfp4_n_split", &mxfp4_n_split_py,
+          "split-K count of mxfp4_gemm for (N, K)");
   mod.def("prefill_attn_lse", &prefill_attn_lse,
           "causal GQA prefill attention returning (out, logsumexp)");
   mod.def("attn_bwd", &attn_bwd,

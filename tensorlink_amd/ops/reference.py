@@ -286,3 +286,38 @@ def moe_topk_router(router_logits: torch.Tensor, top_k: int
     weights, idx = probs.topk(top_k, dim=-1)
     weights = weights / weights.sum(-1, keepdim=True)
     return weights, idx
+
+
+# --------------------------------------------------------------------------
+# MXFP4 (OCP microscaling fp4) weight-only linear
+# --------------------------------------------------------------------------
+_E2M1_VALUES = torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0])
+
+
+def dequantize_mxfp4(packed: torch.Tensor, exponents: torch.Tensor,
+                     group: int = 32, dtype=torch.float32):
+    """packed [N, K/2] uint8 (element 2i low nibble, 2i+1 high nibble; code
+    bit 3 sign, bits 0-2 index {0,.5,1,1.5,2,3,4,6}) and exponents
+    [N, K/group] int8 (unbiased power of two) -> [N, K] in ``dtype``. An
+    e2m1 value times a power of two has at most 2 significant bits, so
+    the result is exact in bf16 as well as fp32."""
+    N = packed.shape[0]
+    K = packed.shape[1] * 2
+    code = torch.empty(N, K, dtype=torch.uint8, device=packed.device)
+    code[:, 0::2] = packed & 0xF
+    code[:, 1::2] = packed >> 4
+    vals = _E2M1_VALUES.to(packed.device)
+    mag = vals[(code & 0x7).long()]
+    sign = torch.where((code & 0x8) != 0, -1.0, 1.0)
+    scale = torch.pow(2.0, exponents.float()).repeat_interleave(group, -1)
+    return (mag * sign * scale).to(dtype)
+
+
+def mxfp4_linear(x: torch.Tensor, packed: torch.Tensor,
+                 exponents: torch.Tensor,
+                 bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x @ dequant(packed, exponents)^T + bias in fp32, cast to x.dtype:
+    the contract of ops/csrc/mxfp4_gemm.hip."""
+    w = dequantize_mxfp4(packed, exponents, dtype=torch.float32)
+    y = F.linear(x.float(), w, bias.float() if bias is not None else None)
+    return y.to(x.dtype)

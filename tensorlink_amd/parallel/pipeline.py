@@ -120,8 +120,13 @@ class PipelineRunner:
                 self._no_graph = True
         elif quantize == "fp4-dense":
             from tensorlink_amd.models.quant import quantize_dense_fp4
+            from tensorlink_amd import ops as _ops
             quantize_dense_fp4(self.stage)
-            self._no_graph = True
+            # same rule as fp8-dense: with the extension the projections
+            # run mxfp4_gemm.hip (no host sync, capture-safe); only the
+            # per-call dequant fallback keeps decode eager
+            if not _ops.extension_loaded():
+                self._no_graph = True
         self.stage.eval()
         self.p2p = P2P(rank, world, group, rank_base) if world > 1 else None
         self.is_first = rank == 0
