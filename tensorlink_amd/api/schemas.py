@@ -19,7 +19,7 @@ class JobRequest(BaseModel):
     max_ctx: int = 4096
     prefill_chunk: Optional[int] = None
     prefix_caching: bool = False
-    quantize: Optional[str] = None    # fp8 | fp8-dense | fp4-dense
+    quantize: Optional[str] = None    # fp8 | fp8-dense | fp4 | fp4-dense
 
 
 class GenerationRequest(BaseModel):

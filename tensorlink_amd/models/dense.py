@@ -235,35 +235,55 @@ class MoEMLP(nn.Module):
                                       for _ in range(self.num_experts)])
 
     def _fused_kind(self):
-        """"bf16" / "fp8" when every expert is uniform and the grouped
-        kernel (ops/csrc/moe_gemm.hip) can serve this block; None falls
-        back to the per-expert loop (CPU, training, fp4)."""
-        from tensorlink_amd.models.quant import Fp8Linear
+        """"bf16" / "fp8" / "fp4" when every expert is uniform and a
+        grouped kernel (ops/csrc/moe_gemm.hip, mxfp4_moe_gemm.hip) can
+        serve this block; None falls back to the per-expert loop (CPU,
+        training, fp4 shapes the kernel does not take)."""
+        from tensorlink_amd.models.quant import Fp4Linear, Fp8Linear
         e0 = self.experts[0]
         if isinstance(e0.gate_up_proj, Fp8Linear):
             return "fp8"
+        if isinstance(e0.gate_up_proj, Fp4Linear):
+            # every projection of every expert: bias-free MXFP4 in a
+            # shape mxfp4_moe_gemm.hip takes (N % 64, K % 128)
+            for e in self.experts:
+                for p in (e.gate_up_proj, e.down_proj):
+                    if not (isinstance(p, Fp4Linear) and p.bias is None
+                            and p.out_features % 64 == 0
+                            and p.in_features % 128 == 0):
+                        return None
+            return "fp4"
         if isinstance(e0.gate_up_proj, nn.Linear) \
                 and e0.gate_up_proj.bias is None:
             return "bf16"
         return None
 
-    def _tables(self, dev, fp8):
+    def _tables(self, dev, kind):
         """Device pointer tables into the per-expert weights (no stacked
-        copy); rebuilt if weights moved."""
-        gus = [(e.gate_up_proj.weight_fp8 if fp8 else e.gate_up_proj.weight)
-               for e in self.experts]
-        key = (str(dev), fp8, gus[0].data_ptr())
+        copy); rebuilt if weights moved. The second pair holds what goes
+        with the weights: fp8 per-channel scales, fp4 group exponents."""
+        wname = {"fp8": "weight_fp8", "fp4": "packed"}.get(kind, "weight")
+        sname = {"fp8": "scale", "fp4": "exponents"}.get(kind)
+        gus = [getattr(e.gate_up_proj, wname) for e in self.experts]
+        key = (str(dev), kind, gus[0].data_ptr())
         if getattr(self, "_tbl_key", None) != key:
-            downs = [(e.down_proj.weight_fp8 if fp8 else e.down_proj.weight)
-                     for e in self.experts]
-            mk = lambda ts: torch.tensor([t.data_ptr() for t in ts],
-                                         dtype=torch.int64, device=dev)
+            downs = [getattr(e.down_proj, wname) for e in self.experts]
+
+            def mk(ts):
+                if kind == "fp4":
+                    # the kernel loads 16 B per lane from dense rows
+                    assert all(t.is_contiguous()
+                               and t.data_ptr() % 16 == 0 for t in ts), \
+                        "fp4 expert tensors must be contiguous and " \
+                        "16-byte aligned"
+                return torch.tensor([t.data_ptr() for t in ts],
+                                    dtype=torch.int64, device=dev)
             self._gu_ptrs = mk(gus)
             self._down_ptrs = mk(downs)
-            if fp8:
-                self._gu_scales = mk([e.gate_up_proj.scale
+            if sname is not None:
+                self._gu_scales = mk([getattr(e.gate_up_proj, sname)
                                       for e in self.experts])
-                self._down_scales = mk([e.down_proj.scale
+                self._down_scales = mk([getattr(e.down_proj, sname)
                                         for e in self.experts])
             else:
                 self._gu_scales = self._down_scales = None
@@ -271,17 +291,18 @@ class MoEMLP(nn.Module):
         return (self._gu_ptrs, self._down_ptrs, self._gu_scales,
                 self._down_scales)
 
-    def _fused_forward(self, flat, rw, idx, fp8):
+    def _fused_forward(self, flat, rw, idx, kind=None):
         """Grouped expert GEMMs over expert-sorted (token, slot) pairs;
         deterministic combine: inverse-permutation gather then a fixed
         slot-order sum (no atomics — batcher greedy equality holds for
         MoE models too). hipGraph-capture-safe end to end."""
         C = ops._require_ext()
+        kind = kind if kind is not None else self._fused_kind()
         E, k = self.num_experts, self.top_k
         T, H = flat.shape
         P = T * k
         dev = flat.device
-        gu_p, down_p, gu_s, down_s = self._tables(dev, fp8)
+        gu_p, down_p, gu_s, down_s = self._tables(dev, kind)
         fi = idx.reshape(-1)
         order = fi.argsort(stable=True)
         # counts via scatter_add (torch.bincount device-syncs, which
@@ -292,10 +313,17 @@ class MoEMLP(nn.Module):
         seg[1:] = counts.cumsum(0)
         pair_tok = (order // k).to(torch.int32)
         Ie = self.experts[0].inter
-        gu = C.moe_gemm(flat.contiguous(), pair_tok, seg, gu_p, gu_s,
-                        2 * Ie, fp8)
-        act = ops.swiglu_fused(gu)
-        y_pairs = C.moe_gemm(act, None, seg, down_p, down_s, H, fp8)
+        if kind == "fp4":
+            gu = ops.mxfp4_moe_gemm(flat.contiguous(), pair_tok, seg, gu_p,
+                                    gu_s, 2 * Ie)
+            act = ops.swiglu_fused(gu)
+            y_pairs = ops.mxfp4_moe_gemm(act, None, seg, down_p, down_s, H)
+        else:
+            fp8 = kind == "fp8"
+            gu = C.moe_gemm(flat.contiguous(), pair_tok, seg, gu_p, gu_s,
+                            2 * Ie, fp8)
+            act = ops.swiglu_fused(gu)
+            y_pairs = C.moe_gemm(act, None, seg, down_p, down_s, H, fp8)
         y_pairs = y_pairs * rw.reshape(-1)[order].unsqueeze(1)
         inv = torch.empty_like(order)
         inv[order] = torch.arange(P, device=dev, dtype=order.dtype)
@@ -310,8 +338,7 @@ class MoEMLP(nn.Module):
                 and not torch.is_grad_enabled() and ops.extension_loaded()):
             kind = self._fused_kind()
             if kind is not None:
-                out = self._fused_forward(flat, weights, idx,
-                                          kind == "fp8")
+                out = self._fused_forward(flat, weights, idx, kind)
                 return out.reshape(B, S, H)
         out = torch.zeros_like(flat)
         for e in range(self.num_experts):

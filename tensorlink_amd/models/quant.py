@@ -184,6 +184,18 @@ def quantize_mxfp4(w: torch.Tensor, group: int = 32):
     return packed, e.to(torch.int8)
 
 
+def quantize_mxfp4_rows(w: torch.Tensor, rows: int = 4096):
+    """quantize_mxfp4 in blocks of ``rows`` rows. Its argmin temporary is
+    32 B per element (about 3.7 GB for one Mixtral gate_up expert); rows
+    are quantized independently, so the tensors are identical to the
+    one-shot call's."""
+    if w.shape[0] <= rows:
+        return quantize_mxfp4(w)
+    ps, es = zip(*(quantize_mxfp4(w[i:i + rows])
+                   for i in range(0, w.shape[0], rows)))
+    return torch.cat(ps), torch.cat(es)
+
+
 class Fp4Linear(nn.Module):
     """Weight-only MXFP4 linear: 4x smaller weights than bf16. Forward
     goes through ops.mxfp4_linear: on GPU the packed weights feed the
@@ -202,7 +214,7 @@ class Fp4Linear(nn.Module):
 
     @classmethod
     def from_linear(cls, lin: nn.Linear) -> "Fp4Linear":
-        packed, e = quantize_mxfp4(lin.weight.detach())
+        packed, e = quantize_mxfp4_rows(lin.weight.detach())
         return cls(packed, e, lin.bias, lin.in_features, lin.out_features)
 
     def forward(self, x):
@@ -210,9 +222,31 @@ class Fp4Linear(nn.Module):
         return ops.mxfp4_linear(x, self.packed, self.exponents, self.bias)
 
 
+def quantize_experts_fp4(stage: nn.Module) -> int:
+    """Convert every MoE expert Linear in a stage to Fp4Linear in place
+    (4-bit analog of quantize_experts_fp8; attention, embeddings, norms,
+    the router and the LM head keep their dtype). On GPU the block then
+    runs the grouped kernel (ops/csrc/mxfp4_moe_gemm.hip) where the expert
+    shapes allow it, the per-expert loop over mxfp4_gemm.hip elsewhere.
+    Returns the number of converted layers."""
+    from tensorlink_amd.models.dense import MoEMLP
+    n = 0
+    for mod in stage.modules():
+        if isinstance(mod, MoEMLP):
+            for expert in mod.experts:
+                for name in ("gate_up_proj", "down_proj"):
+                    lin = getattr(expert, name)
+                    if isinstance(lin, nn.Linear):
+                        setattr(expert, name, Fp4Linear.from_linear(lin))
+                        n += 1
+    return n
+
+
 def quantize_dense_fp4(stage: nn.Module) -> int:
     """Convert every projection Linear to weight-only MXFP4 in place
-    (4-bit analog of quantize_dense_fp8)."""
+    (4-bit analog of quantize_dense_fp8). On an MoE model this covers the
+    expert projections too, which then take the grouped kernel like
+    quantize_experts_fp4's."""
     n = 0
     targets = ("qkv_proj", "o_proj", "gate_up_proj", "down_proj")
     for mod in stage.modules():

@@ -432,6 +432,31 @@ def mxfp4_linear(x: torch.Tensor, packed: torch.Tensor,
         x, w.to(x.dtype), bias.to(x.dtype) if bias is not None else None)
 
 
+# incremented whenever mxfp4_moe_gemm.hip handles a grouped expert GEMM
+# (same purpose as mxfp4_dispatch_count)
+mxfp4_moe_dispatch_count = 0
+
+
+def mxfp4_moe_gemm(x: torch.Tensor, tok_idx: Optional[torch.Tensor],
+                   seg_off: torch.Tensor, p_ptrs: torch.Tensor,
+                   e_ptrs: torch.Tensor, N: int) -> torch.Tensor:
+    """Grouped MXFP4 expert GEMM (ops/csrc/mxfp4_moe_gemm.hip), GPU only:
+    out[p] = x[tok_idx[p]] @ dequant(packed_e, exponents_e)^T for the pair
+    rows p of segment e = [seg_off[e], seg_off[e+1]). x bf16 [T, K] (or
+    [P, K] with tok_idx None); tok_idx [P] and seg_off [E+1] int32;
+    p_ptrs / e_ptrs [E] int64 device addresses of each expert's packed
+    [N, K/2] uint8 and exponents [N, K/32] int8, 16-byte aligned and
+    contiguous. Needs N % 64 == 0 and K % 128 == 0. One launch, no host
+    sync, hipGraph-capturable; a pair's row is bitwise independent of the
+    rest of the call. The CPU contract is
+    ops.reference.mxfp4_moe_grouped."""
+    global mxfp4_moe_dispatch_count
+    out = _require_ext().mxfp4_moe_gemm(x, tok_idx, seg_off, p_ptrs, e_ptrs,
+                                        N)
+    mxfp4_moe_dispatch_count += 1
+    return out
+
+
 # ---------------------------------------------------------------------------
 # AdamW
 # ---------------------------------------------------------------------------

@@ -60,6 +60,11 @@ void tl_moe_gemm(const void* x, const void* tok_idx, const void* seg_off,
 void tl_mxfp4_gemm(const void* x, const void* packed, const void* exps,
                    const void* bias, void* out, void* partial, int M, int N,
                    int K, int n_split, hipStream_t stream);
+void tl_mxfp4_moe_gemm(const void* x, const void* tok_idx,
+                       const void* seg_off, const void* p_ptrs,
+                       const void* e_ptrs, void* out, void* partial, int T,
+                       int P, int E, int N, int K, int n_split,
+                       hipStream_t stream);
 void tl_prefill_attn_lse(const void* q, const void* k, const void* v,
                          void* out, void* lse, int B, int Sq, int Skv,
                          int q_off, int Hq, int Hkv, int D, float scale,
@@ -424,18 +429,36 @@ Tensor skinny_gemm(Tensor x, Tensor w, c10::optional<Tensor> bias) {
 // Split-K policy of the MXFP4 weight GEMM (mxfp4_gemm.hip). (N,K)-pure like
 // gemm_n_split, but counted in the kernel's 128-k steps: a column's packed
 // bytes are 4x fewer than bf16, so a split must keep >= 2 steps.
-static int mxfp4_n_split(int N, int K) {
+// One loop serves both MXFP4 kernels: `blocks` is the grid before the
+// split, N/64 for the dense kernel and (N/64)*E for the grouped one.
+static int mxfp4_split_for_blocks(int blocks, int K) {
   int n_split = 1;
-  while ((N / 64) * n_split < 256 && n_split < 8 &&
+  while (blocks * n_split < 256 && n_split < 8 &&
          (K / 128) / (n_split * 2) >= 2)
     n_split <<= 1;
   return n_split;
+}
+
+static int mxfp4_n_split(int N, int K) {
+  return mxfp4_split_for_blocks(N / 64, K);
+}
+
+// Grouped expert kernel (mxfp4_moe_gemm.hip): pure in (N, K, E), never P
+// or the routing, so a pair's row is the same in every call.
+static int mxfp4_moe_n_split(int N, int K, int E) {
+  return mxfp4_split_for_blocks((N / 64) * E, K);
 }
 
 int64_t mxfp4_n_split_py(int64_t N, int64_t K) {
   TORCH_CHECK(N > 0 && K > 0 && N % 64 == 0 && K % 128 == 0,
               "unsupported shape");
   return mxfp4_n_split((int)N, (int)K);
+}
+
+int64_t mxfp4_moe_n_split_py(int64_t N, int64_t K, int64_t E) {
+  TORCH_CHECK(N > 0 && K > 0 && E > 0 && N % 64 == 0 && K % 128 == 0,
+              "unsupported shape");
+  return mxfp4_moe_n_split((int)N, (int)K, (int)E);
 }
 
 Tensor mxfp4_gemm(Tensor x, Tensor packed, Tensor exponents,
@@ -554,6 +577,66 @@ Tensor moe_gemm(Tensor x, c10::optional<Tensor> tok_idx, Tensor seg_off,
   return out;
 }
 
+// x [T, K] bf16 (or [P, K] pair rows when tok_idx is absent); p_ptrs /
+// e_ptrs: [E] int64 device addresses of each expert's packed [N, K/2]
+// uint8 and exponents [N, K/32] int8 (16-byte aligned, contiguous: the
+// caller's table builder asserts it, the addresses cannot be read here
+// without a sync). n_split_override > 0 is for measurement only.
+Tensor mxfp4_moe_gemm(Tensor x, c10::optional<Tensor> tok_idx,
+                      Tensor seg_off, Tensor p_ptrs, Tensor e_ptrs,
+                      int64_t N, int64_t n_split_override) {
+  CHECK_IN(x, torch::kBFloat16);
+  CHECK_IN(seg_off, torch::kInt);
+  CHECK_IN(p_ptrs, torch::kLong);
+  CHECK_IN(e_ptrs, torch::kLong);
+  TORCH_CHECK(x.dim() == 2, "x must be [T, K]");
+  const int64_t T = x.size(0);
+  const int64_t K = x.size(1);
+  TORCH_CHECK(K > 0 && N > 0 && N % 64 == 0 && K % 128 == 0,
+              "unsupported shape: need N % 64 == 0 and K % 128 == 0");
+  TORCH_CHECK(p_ptrs.dim() == 1 && e_ptrs.dim() == 1 &&
+                  p_ptrs.size(0) == e_ptrs.size(0),
+              "pointer tables must both be [E]");
+  const int64_t E = p_ptrs.size(0);
+  TORCH_CHECK(E >= 1 && E <= 65535, "need 1 <= E <= 65535");
+  TORCH_CHECK(seg_off.dim() == 1 && seg_off.size(0) == E + 1,
+              "seg_off must be [E+1]");
+  TORCH_CHECK(seg_off.device() == x.device() &&
+                  p_ptrs.device() == x.device() &&
+                  e_ptrs.device() == x.device(),
+              "operands must share a device");
+  const void* ti = nullptr;
+  int64_t P = T;
+  if (tok_idx.has_value()) {
+    CHECK_IN(tok_idx.value(), torch::kInt);
+    TORCH_CHECK(tok_idx->dim() == 1, "tok_idx must be [P]");
+    TORCH_CHECK(tok_idx->device() == x.device(),
+                "operands must share a device");
+    ti = tok_idx->data_ptr();
+    P = tok_idx->size(0);
+  }
+  TORCH_CHECK(P * N < (int64_t)1 << 31 && T * K < (int64_t)1 << 40,
+              "mxfp4_moe_gemm: call too large");
+  auto out = torch::empty({P, N}, x.options());
+  if (P == 0) return out;
+  TORCH_CHECK(T >= 1, "x has no rows");
+  const int n_split = n_split_override > 0
+                          ? (int)n_split_override
+                          : mxfp4_moe_n_split((int)N, (int)K, (int)E);
+  TORCH_CHECK(n_split >= 1 && n_split <= 8, "bad split count");
+  Tensor partial;
+  void* pp = nullptr;
+  if (n_split > 1) {
+    partial = torch::empty({(int64_t)n_split * P * N},
+                           x.options().dtype(torch::kFloat));
+    pp = partial.data_ptr();
+  }
+  tl_mxfp4_moe_gemm(x.data_ptr(), ti, seg_off.data_ptr(), p_ptrs.data_ptr(),
+                    e_ptrs.data_ptr(), out.data_ptr(), pp, (int)T, (int)P,
+                    (int)E, (int)N, (int)K, n_split, cur_stream());
+  return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
@@ -579,6 +662,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "weight-only MXFP4 GEMM: x @ dequant(packed, exponents)^T + bias");
   mod.def("mxfp4_n_split", &mxfp4_n_split_py,
           "split-K count of mxfp4_gemm for (N, K)");
+  mod.def("mxfp4_moe_gemm", &mxfp4_moe_gemm,
+          "grouped MXFP4 expert GEMM over expert-sorted pair rows",
+          pybind11::arg("x"), pybind11::arg("tok_idx"),
+          pybind11::arg("seg_off"), pybind11::arg("p_ptrs"),
+          pybind11::arg("e_ptrs"), pybind11::arg("N"),
+          pybind11::arg("n_split_override") = 0);
+  mod.def("mxfp4_moe_n_split", &mxfp4_moe_n_split_py,
+          "split-K count of mxfp4_moe_gemm for (N, K, E)");
   mod.def("prefill_attn_lse", &prefill_attn_lse,
           "causal GQA prefill attention returning (out, logsumexp)");
   mod.def("attn_bwd", &attn_bwd,

@@ -30,26 +30,20 @@
 // Split-K: fp32 partial slabs [SPLITK, M, N] and an s-ordered reduce
 // kernel; the split count comes from the host and depends on (N, K) only.
 
-#include "common.hpp"
+#include "mxfp4_common.hpp"
 
 namespace {
 
-constexpr int BLOCK = 256;
-constexpr int KSTEP = 128;                 // k per main-loop step
-constexpr int ROW_BYTES = KSTEP * 2;       // one slab row (bf16)
-constexpr int LUT_BYTES = 256 * 8;         // byte -> float2
+// decode, table build, split slice and reduce: mxfp4_common.hpp, shared
+// with the grouped expert kernel (mxfp4_moe_gemm.hip)
+constexpr int BLOCK = MX_BLOCK;
+constexpr int KSTEP = MX_KSTEP;            // k per main-loop step
+constexpr int ROW_BYTES = MX_ROW_BYTES;    // one slab row (bf16)
+constexpr int LUT_BYTES = MX_LUT_BYTES;    // byte -> float2
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
+using f32x2 = mx_f32x2;
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
-// e2m1 code (4 bits) -> f32, exact
-DEVINLINE float e2m1_to_f32(int c) {
-  const int m = c & 7;
-  const float v = m < 2 ? 0.5f * (float)m
-                        : 0.25f * (float)((2 + (m & 1)) << (m >> 1));
-  return (c & 8) ? -v : v;
-}
 
 template <int MT, int HAS_BIAS, int SPLIT>
 __global__ __launch_bounds__(BLOCK, 2) void mxfp4_gemm_kernel(
@@ -69,9 +63,8 @@ __global__ __launch_bounds__(BLOCK, 2) void mxfp4_gemm_kernel(
   const int quad = lane >> 4;
   const int oc = blockIdx.x * 64 + wave * 16 + col;   // output column
 
-  const int steps = K / KSTEP;
   const int split = SPLIT ? blockIdx.y : 0;
-  const int k_per = SPLIT ? ((steps + n_split - 1) / n_split) * KSTEP : K;
+  const int k_per = SPLIT ? mxfp4_k_per(K, n_split) : K;
   const int k_begin = split * k_per;
   const int k_end = min(K, k_begin + k_per);
 
@@ -79,13 +72,7 @@ __global__ __launch_bounds__(BLOCK, 2) void mxfp4_gemm_kernel(
   __shared__ __attribute__((aligned(16))) unsigned char
       smem[2 * SLAB_BYTES + LUT_BYTES];
   unsigned char* const lut = smem + 2 * SLAB_BYTES;
-  {
-    const int b = threadIdx.x;             // BLOCK == 256 entries
-    f32x2 v;
-    v[0] = e2m1_to_f32(b & 15);
-    v[1] = e2m1_to_f32(b >> 4);
-    *reinterpret_cast<f32x2*>(lut + b * 8) = v;
-  }
+  mxfp4_build_lut(lut);
 
   // this lane's packed row (16 B per 128-k step at dword4 index quad) and
   // exponent row (1 B per step at byte index quad)
@@ -183,19 +170,6 @@ __global__ __launch_bounds__(BLOCK, 2) void mxfp4_gemm_kernel(
     // overwrites buffer 0
     __syncthreads();
   }
-}
-
-template <int HAS_BIAS>
-__global__ void mxfp4_reduce_kernel(const float* __restrict__ partial,
-                                    const bf16* __restrict__ bias,
-                                    bf16* __restrict__ out, int64_t MN,
-                                    int N, int n_split) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= MN) return;
-  float acc = 0.f;
-  for (int s = 0; s < n_split; ++s) acc += partial[s * MN + i];
-  if (HAS_BIAS) acc += bf2f(bias[i % N]);
-  out[i] = f2bf(acc);
 }
 
 }  // namespace

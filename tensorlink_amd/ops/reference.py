@@ -321,3 +321,26 @@ def mxfp4_linear(x: torch.Tensor, packed: torch.Tensor,
     w = dequantize_mxfp4(packed, exponents, dtype=torch.float32)
     y = F.linear(x.float(), w, bias.float() if bias is not None else None)
     return y.to(x.dtype)
+
+
+def mxfp4_moe_grouped(x: torch.Tensor, tok_idx: Optional[torch.Tensor],
+                      seg_off: torch.Tensor, packed, exponents
+                      ) -> torch.Tensor:
+    """out[p] = x[tok_idx[p]] @ dequant(packed[e], exponents[e])^T in fp32,
+    cast to x.dtype, for the pair rows p of segment e = [seg_off[e],
+    seg_off[e+1]); tok_idx None means x holds the pair rows themselves.
+    packed / exponents are per-expert sequences. The contract of
+    ops/csrc/mxfp4_moe_gemm.hip (which takes the same tensors through
+    pointer tables)."""
+    P = x.shape[0] if tok_idx is None else tok_idx.shape[0]
+    N = packed[0].shape[0]
+    out = torch.zeros(P, N, dtype=torch.float32, device=x.device)
+    seg = seg_off.tolist()
+    for e in range(len(packed)):
+        a, b = seg[e], seg[e + 1]
+        if b <= a:
+            continue
+        rows = x[a:b] if tok_idx is None else x[tok_idx[a:b].long()]
+        w = dequantize_mxfp4(packed[e], exponents[e], dtype=torch.float32)
+        out[a:b] = rows.float() @ w.t()
+    return out.to(x.dtype)

@@ -182,6 +182,15 @@ def build_ep_model(config_or_name, ep_rank: int, ep: int, device=None,
                 for name in ("gate_up_proj", "down_proj"):
                     setattr(expert, name,
                             Fp8Linear.from_linear(getattr(expert, name)))
+    elif quantize == "fp4":
+        # EP's per-expert loops keep Fp4Linear and the dense MXFP4 kernel
+        # (a grouped kernel for the exchange path is open work)
+        from tensorlink_amd.models.quant import Fp4Linear
+        for layer in stage.layers:
+            for expert in layer.mlp.experts:
+                for name in ("gate_up_proj", "down_proj"):
+                    setattr(expert, name,
+                            Fp4Linear.from_linear(getattr(expert, name)))
     stage.to(device=device, dtype=dtype)
     stage.eval()
     return stage

@@ -118,6 +118,16 @@ class PipelineRunner:
             # existing RuntimeError catch
             if not _ops.extension_loaded():
                 self._no_graph = True
+        elif quantize == "fp4":
+            from tensorlink_amd import ops as _ops
+            from tensorlink_amd.models.quant import quantize_experts_fp4
+            quantize_experts_fp4(self.stage)
+            # MXFP4 experts run the grouped mxfp4_moe_gemm kernel (or the
+            # per-expert mxfp4_gemm loop on shapes it does not take, which
+            # a capture attempt turns into eager decode); without the
+            # extension every call dequantizes, so decode stays eager
+            if not _ops.extension_loaded():
+                self._no_graph = True
         elif quantize == "fp4-dense":
             from tensorlink_amd.models.quant import quantize_dense_fp4
             from tensorlink_amd import ops as _ops
