@@ -71,6 +71,17 @@ class TLLinear(nn.Linear):
         return ops.linear(x, self.weight, self.bias)
 
 
+def _project(mod: nn.Module, x: torch.Tensor, allow_bias: bool = False):
+    """mod(x) for a caller whose next kernel can sum split-K partials
+    itself: a plain bf16 TLLinear hands back ops.Partials where the GEMM
+    family splits K (no reduce pass, no bf16 round trip); anything else —
+    fp8/fp4, LoRA-wrapped or TP-sharded projections, shapes the family
+    does not take — is called as usual and returns its tensor."""
+    if type(mod) is TLLinear and (allow_bias or mod.bias is None):
+        return ops.linear_partials(x, mod.weight, mod.bias)
+    return mod(x)
+
+
 def compute_inv_freq(config: ModelConfig) -> torch.Tensor:
     """RoPE inverse frequencies, honoring HF rope_scaling. Implements
     the Llama-3.1 "llama3" spectrum scaling (long wavelengths divided by
@@ -127,10 +138,18 @@ class Attention(nn.Module):
 
     def forward(self, x: torch.Tensor, positions: torch.Tensor,
                 kv_cache: Optional[KVCache] = None, layer_idx: int = 0,
-                training: bool = False) -> torch.Tensor:
+                training: bool = False, fuse: bool = False):
+        """fuse (cached inference only): the caller's next kernel sums
+        split-K partials itself, so o_proj may come back as ops.Partials;
+        qkv goes to rope_append as partials + bias, and decode attention
+        takes the +1 length offset as an argument."""
         B, S, H = x.shape
         eps = self.config.rms_norm_eps
-        qkv = self.qkv_proj(x)
+        fuse = fuse and kv_cache is not None and not training
+        if fuse and not self.use_qk_norm:
+            qkv = _project(self.qkv_proj, x, allow_bias=True)
+        else:
+            qkv = self.qkv_proj(x)
         flat_pos = positions.reshape(-1)
 
         if training or kv_cache is None:
@@ -166,11 +185,18 @@ class Attention(nn.Module):
             k = ops.rmsnorm(k.contiguous(), self.k_norm.to(k.dtype), eps)
             qkv = torch.cat([q.reshape(B, S, -1), k.reshape(B, S, -1),
                              v.reshape(B, S, -1)], dim=-1)
-        q = ops.rope_append_(qkv.reshape(B * S, -1), kv_cache.k[layer_idx],
+        if not isinstance(qkv, ops.Partials):
+            qkv = qkv.reshape(B * S, -1)
+        q = ops.rope_append_(qkv, kv_cache.k[layer_idx],
                              kv_cache.v[layer_idx], flat_pos, self.inv_freq,
                              S, self.n_heads, self.n_kv, block_table=table)
         q = q.view(B, S, self.n_heads, self.head_dim)
-        if S == 1:
+        if S == 1 and fuse:
+            out = ops.attention_decode(
+                q, kv_cache.k[layer_idx], kv_cache.v[layer_idx],
+                kv_cache.seq_lens, scale=self.scale, block_table=table,
+                len_add=1)
+        elif S == 1:
             out = ops.attention_decode(
                 q, kv_cache.k[layer_idx], kv_cache.v[layer_idx],
                 kv_cache.seq_lens + 1, scale=self.scale, block_table=table)
@@ -196,6 +222,8 @@ class Attention(nn.Module):
                 k_attn, v_attn = kv_cache.gather_contiguous(layer_idx, kv_len)
             out = ops.attention_prefill(q, k_attn, v_attn, causal=True,
                                         scale=self.scale, q_off=off)
+        if fuse:
+            return _project(self.o_proj, out.reshape(B, S, -1))
         return self.o_proj(out.reshape(B, S, -1))
 
 
@@ -208,12 +236,14 @@ class MLP(nn.Module):
         self.gate_up_proj = TLLinear(h, 2 * i, bias=False)
         self.down_proj = TLLinear(i, h, bias=False)
 
-    def forward(self, x):
+    def forward(self, x, fuse: bool = False):
         gu = self.gate_up_proj(x)
         if torch.is_grad_enabled() and gu.requires_grad:
             gate, up = gu.split([self.inter, self.inter], dim=-1)
             return self.down_proj(ops.swiglu(gate.contiguous(),
                                              up.contiguous()))
+        if fuse:    # may return ops.Partials (see _project)
+            return _project(self.down_proj, ops.swiglu_fused(gu))
         return self.down_proj(ops.swiglu_fused(gu))
 
 
@@ -379,6 +409,33 @@ class DecoderLayer(nn.Module):
         h, hidden = ops.rmsnorm_residual(attn_out, hidden, w_post, eps)
         return hidden + self.mlp(h)
 
+    def forward_carry(self, residual, pending, positions, kv_cache=None,
+                      layer_idx=0):
+        """Inference forward that leaves this layer's last residual add to
+        whoever runs next. The stream entering the layer is
+        ``residual + pending`` (pending None: just residual); returns the
+        same pair for the layer's output, with pending = the MLP result —
+        a tensor, or ops.Partials straight from the down-proj GEMM. The
+        next layer's input norm (or the head's final norm) does the add,
+        so the stream is written once per layer instead of twice, and the
+        o_proj / down_proj split-K reduces happen inside the norm kernels.
+        Bitwise equal to forward(): add_rmsnorm(rounded=True) is "bf16
+        add, then rmsnorm", rounded=False is rmsnorm_residual."""
+        eps = self.config.rms_norm_eps
+        w_in = self.input_layernorm.to(residual.dtype)
+        w_post = self.post_attention_layernorm.to(residual.dtype)
+        if pending is None:
+            h = ops.rmsnorm(residual, w_in, eps)
+        else:
+            h, residual = ops.add_rmsnorm(pending, residual, w_in, eps,
+                                          rounded=True)
+        attn_out = self.self_attn(h, positions, kv_cache, layer_idx, False,
+                                  fuse=True)
+        h, residual = ops.add_rmsnorm(attn_out, residual, w_post, eps)
+        if type(self.mlp) is MLP:
+            return residual, self.mlp(h, fuse=True)
+        return residual, self.mlp(h)
+
 
 class StageModel(nn.Module):
     """A contiguous slice of the decoder living on one rank."""
@@ -425,9 +482,16 @@ class StageModel(nn.Module):
         w = self.embed_tokens.weight
         return self.embed_tokens(input_ids).to(w.dtype)
 
-    def head(self, hidden: torch.Tensor) -> torch.Tensor:
-        h = ops.rmsnorm(hidden, self.norm.to(hidden.dtype),
-                        self.config.rms_norm_eps)
+    def head(self, hidden: torch.Tensor, pending=None) -> torch.Tensor:
+        """Final norm + lm_head. pending: a last-layer MLP result still to
+        be added to ``hidden`` (forward_carry) — folded into the norm."""
+        if pending is None:
+            h = ops.rmsnorm(hidden, self.norm.to(hidden.dtype),
+                            self.config.rms_norm_eps)
+        else:
+            h, _ = ops.add_rmsnorm(pending, hidden,
+                                   self.norm.to(hidden.dtype),
+                                   self.config.rms_norm_eps, rounded=True)
         if self.config.tie_word_embeddings and self.has_embedding:
             return h @ self.embed_tokens.weight.t()
         return self.lm_head(h)
@@ -442,6 +506,20 @@ class StageModel(nn.Module):
             hidden = hidden_or_ids
         ckpt = (training and getattr(self, "grad_checkpointing", False)
                 and torch.is_grad_enabled())
+        if not training and ops.decode_fusion_enabled() and len(self.layers):
+            # inference: each layer's closing residual add rides into the
+            # next layer's input norm (DecoderLayer.forward_carry)
+            pending = None
+            for i, layer in enumerate(self.layers):
+                hidden, pending = layer.forward_carry(hidden, pending,
+                                                      positions, kv_cache, i)
+            if kv_cache is not None:
+                kv_cache.advance(hidden.shape[1])
+            if self.has_head and return_logits:
+                return self.head(hidden, pending)
+            # no head here: materialise the stream, so what leaves the
+            # stage is what the unfused chain produced
+            return ops.add_residual(pending, hidden)
         for i, layer in enumerate(self.layers):
             if ckpt:
                 # recompute the layer in backward instead of stashing

@@ -84,6 +84,77 @@ def rmsnorm_residual(x: torch.Tensor, residual: torch.Tensor,
     return outs[0], outs[1]
 
 
+class Partials:
+    """A projection's result before its split-K reduce: ``data`` is the
+    fp32 partial tensor [n_split, ..., N] of the hand-written GEMM family
+    (:func:`linear_partials`) and ``bias`` its still-unapplied bf16 bias
+    (or None). The value it stands for is
+    bf16(sum_s data[s] (+ bias)) summed from 0 in s order — consumers
+    (:func:`rope_append_`, :func:`add_rmsnorm`, :func:`add_residual`) sum
+    it in-kernel, so the reduce pass and its bf16 round trip never run."""
+
+    __slots__ = ("data", "bias")
+
+    def __init__(self, data: torch.Tensor, bias=None):
+        self.data = data
+        self.bias = bias
+
+    @property
+    def n_split(self) -> int:
+        return self.data.shape[0]
+
+    def materialize(self) -> torch.Tensor:
+        """The bf16 tensor ops.linear would have returned (torch ops; for
+        callers that turn out to need the plain output after all)."""
+        acc = torch.zeros_like(self.data[0])
+        for s in range(self.data.shape[0]):
+            acc = acc + self.data[s]
+        if self.bias is not None:
+            acc = acc + self.bias.float()
+        return acc.to(torch.bfloat16)
+
+
+def add_rmsnorm(x, residual: torch.Tensor, weight: torch.Tensor,
+                eps: float = 1e-6, rounded: bool = False):
+    """Residual add + RMSNorm in one kernel; ``x`` is a bf16 tensor or a
+    bias-free :class:`Partials`. Returns (y, r) with r = bf16(x + residual).
+
+    rounded=False normalises the unrounded fp32 sum — exactly
+    :func:`rmsnorm_residual`. rounded=True normalises r itself — exactly a
+    bf16 ``x + residual`` followed by :func:`rmsnorm` (the decoder's
+    layer hand-over and final norm). Off the GPU both compose the torch
+    ops the CPU decoder has always run: add in the tensor dtype, norm."""
+    part = isinstance(x, Partials)
+    if not _on_gpu(residual):
+        xt = x.materialize() if part else x
+        r = residual + xt
+        return ref.rmsnorm(r, weight, eps), r
+    if part:
+        assert x.bias is None, "add_rmsnorm takes bias-free partials"
+        xt = x.data
+    else:
+        xt = x.contiguous()
+    y, r = _require_ext().rmsnorm_add_fwd(
+        xt, residual.contiguous(), weight.contiguous(), eps,
+        2 if rounded else 1)
+    return y, r
+
+
+def add_residual(x, residual: torch.Tensor) -> torch.Tensor:
+    """bf16(x + residual) with ``x`` a bf16 tensor or bias-free
+    :class:`Partials` — :func:`add_rmsnorm`'s sum without the norm."""
+    part = isinstance(x, Partials)
+    if not _on_gpu(residual):
+        return residual + (x.materialize() if part else x)
+    if part:
+        assert x.bias is None, "add_residual takes bias-free partials"
+        xt = x.data
+    else:
+        xt = x.contiguous()
+    return _require_ext().rmsnorm_add_fwd(xt, residual.contiguous(), None,
+                                          0.0, 3)[0]
+
+
 # ---------------------------------------------------------------------------
 # RoPE
 # ---------------------------------------------------------------------------
@@ -107,7 +178,7 @@ def apply_rope_(q: torch.Tensor, k: torch.Tensor, positions: torch.Tensor,
     _require_ext().rope_(q, k, positions.int(), inv_freq.float(), sign)
 
 
-def rope_append_(qkv: torch.Tensor, k_cache: torch.Tensor,
+def rope_append_(qkv, k_cache: torch.Tensor,
                  v_cache: torch.Tensor, positions: torch.Tensor,
                  inv_freq: torch.Tensor, S: int, Hq: int, Hkv: int,
                  block_table: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -117,12 +188,25 @@ def rope_append_(qkv: torch.Tensor, k_cache: torch.Tensor,
     [B,Hkv,Smax,D] (or paged pools [n_pages,Hkv,128,D] with block_table
     [B, pages]); positions [T] gives the RoPE angle and cache slot.
     Returns the rotated q as a contiguous [T, Hq, D] tensor.
+
+    qkv may be the projection's :class:`Partials` (reduced + biased
+    in-kernel, same bits). inv_freq may be fp32 or bf16 — the kernel
+    widens bf16 in-register, so no conversion kernel runs per call.
     """
-    if _on_gpu(qkv):
+    part = isinstance(qkv, Partials)
+    if _on_gpu(k_cache):
+        if inv_freq.dtype not in (torch.float32, torch.bfloat16):
+            inv_freq = inv_freq.float()
+        bt = block_table.int() if block_table is not None else None
+        if part:
+            return _require_ext().rope_append_(
+                qkv.data, k_cache, v_cache, positions.int(),
+                inv_freq.contiguous(), S, Hq, Hkv, bt, qkv.bias)
         return _require_ext().rope_append_(
             qkv.contiguous(), k_cache, v_cache, positions.int(),
-            inv_freq.float(), S, Hq, Hkv,
-            block_table.int() if block_table is not None else None)
+            inv_freq.contiguous(), S, Hq, Hkv, bt, None)
+    if part:
+        qkv = qkv.materialize()
     D = k_cache.shape[-1]
     T = qkv.numel() // qkv.shape[-1]
     q = qkv[..., :Hq * D].reshape(T, Hq, D).contiguous()
@@ -287,10 +371,12 @@ def attention_train(q, k, v, causal: bool = True,
 
 def attention_decode(q, k_cache, v_cache, seq_lens,
                      scale: Optional[float] = None, n_split: int = 0,
-                     block_table: Optional[torch.Tensor] = None
-                     ) -> torch.Tensor:
+                     block_table: Optional[torch.Tensor] = None,
+                     len_add: int = 0) -> torch.Tensor:
     """q [B,1,Hq,D] or [B,Hq,D]; caches [B,Hkv,Smax,D] (or paged pools +
-    block_table); seq_lens [B]. n_split: flash-decode splits (0 = auto)."""
+    block_table); seq_lens [B]. n_split: flash-decode splits (0 = auto).
+    Row b attends to its first seq_lens[b] + len_add keys; len_add is
+    added in-kernel, sparing the caller a per-layer tensor add."""
     squeeze = q.dim() == 4
     if squeeze:
         q3 = q.squeeze(1)
@@ -298,6 +384,8 @@ def attention_decode(q, k_cache, v_cache, seq_lens,
         q3 = q
     scale = scale if scale is not None else 1.0 / math.sqrt(q3.shape[-1])
     if not _on_gpu(q3):
+        if len_add:
+            seq_lens = seq_lens + len_add
         if block_table is not None:
             # gather pages -> contiguous [B, L, Hkv, D] for the reference
             B = q3.shape[0]
@@ -318,7 +406,7 @@ def attention_decode(q, k_cache, v_cache, seq_lens,
         return out if squeeze else out.squeeze(1)
     out = _require_ext().decode_attn(
         q3.contiguous(), k_cache, v_cache, seq_lens.int(), scale, n_split,
-        block_table.int() if block_table is not None else None)
+        block_table.int() if block_table is not None else None, len_add)
     return out.unsqueeze(1) if squeeze else out
 
 
@@ -387,6 +475,39 @@ def linear(x: torch.Tensor, weight: torch.Tensor,
                 x.contiguous(), weight,
                 bias.to(torch.bfloat16) if bias is not None else None)
     return torch.nn.functional.linear(x, weight, bias)
+
+
+def decode_fusion_enabled() -> bool:
+    """False under TL_NO_DECODE_FUSION=1: the decoder then runs the
+    unfused chain (every GEMM reduces its own partials, the residual adds
+    are separate kernels) — same bits, kept for A/B runs and tests. Read
+    per call so a test can flip it."""
+    return not _os.environ.get("TL_NO_DECODE_FUSION")
+
+
+def linear_partials(x: torch.Tensor, weight: torch.Tensor,
+                    bias: Optional[torch.Tensor] = None):
+    """:func:`linear` for a caller whose next kernel can consume split-K
+    partials: where the hand-written family would split K, returns
+    :class:`Partials` and skips the reduce pass; everywhere else (other
+    devices/dtypes, M above GEMM_M_MAX, library-routed classes, n_split
+    == 1) returns :func:`linear`'s tensor."""
+    global gemm_dispatch_count
+    if (x.is_cuda and not torch.is_grad_enabled()
+            and x.dtype == torch.bfloat16
+            and not _os.environ.get("TL_NO_SKINNY")):
+        K = x.shape[-1]
+        M = x.numel() // K
+        N = weight.shape[0]
+        if _use_tl_gemm(M, N, K):
+            gemm_dispatch_count += 1
+            b = bias.to(torch.bfloat16) if bias is not None else None
+            out = _require_ext().skinny_gemm_partials(x.contiguous(),
+                                                      weight, b)
+            if out.dtype == torch.float32:
+                return Partials(out, b)
+            return out
+    return linear(x, weight, bias)
 
 
 # ---------------------------------------------------------------------------

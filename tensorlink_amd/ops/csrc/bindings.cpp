@@ -11,6 +11,9 @@ extern "C" {
 void tl_rmsnorm_fwd(const void* x, const void* residual, const void* w,
                     void* y, void* r_out, void* rstd, int64_t N, int H,
                     float eps, hipStream_t stream);
+void tl_rmsnorm_add_fwd(const void* x, const void* residual, const void* w,
+                        void* y, void* r_out, int64_t N, int H, float eps,
+                        int n_split, int mode, hipStream_t stream);
 void tl_rmsnorm_bwd(const void* dy, const void* x, const void* w,
                     const void* rstd, void* dx, void* dw, void* dw_partial,
                     int n_blocks, int64_t N, int H, hipStream_t stream);
@@ -26,15 +29,17 @@ void tl_adamw(void* param, const void* grad, void* m, void* v, int64_t n,
               float weight_decay, int step, hipStream_t stream);
 void tl_decode_attn(const void* q, const void* k_cache, const void* v_cache,
                     const void* seq_lens, void* out, int B, int Hq, int Hkv,
-                    int Smax, int D, float scale, hipStream_t stream);
+                    int Smax, int D, float scale, int len_add,
+                    hipStream_t stream);
 void tl_prefill_attn(const void* q, const void* k, const void* v, void* out,
                      int B, int Sq, int Skv, int q_off, int Hq, int Hkv,
                      int D, float scale, int causal, hipStream_t stream);
-void tl_rope_append(const void* qkv, void* q_out, void* k_cache,
-                    void* v_cache, const void* positions,
+void tl_rope_append(const void* qkv, const void* bias, void* q_out,
+                    void* k_cache, void* v_cache, const void* positions,
                     const void* inv_freq, const void* block_table,
                     int64_t T, int row_stride, int S, int Hq, int Hkv,
-                    int D, int Smax, int bt_stride, hipStream_t stream);
+                    int D, int Smax, int bt_stride, int n_split,
+                    int inv_bf16, hipStream_t stream);
 void tl_swiglu_fused(const void* gu, void* out, int64_t N, int I,
                      hipStream_t stream);
 void tl_decode_attn_mfma(const void* q, const void* k_cache,
@@ -42,13 +47,20 @@ void tl_decode_attn_mfma(const void* q, const void* k_cache,
                          const void* block_table, void* out,
                          void* partial, void* partial_ml, int B, int Hq,
                          int Hkv, int Smax, int D, float scale, int n_split,
-                         int bt_stride, int per_row, hipStream_t stream);
+                         int bt_stride, int per_row, int len_add,
+                         hipStream_t stream);
 void tl_skinny_gemm(const void* x, const void* w, const void* bias,
                     void* out, void* partial, int M, int N, int K,
                     int n_split, hipStream_t stream);
 void tl_gemm_tiled(const void* x, const void* w, const void* bias, void* out,
                    void* partial, int M, int N, int K, int n_split,
                    hipStream_t stream);
+void tl_skinny_gemm_partials(const void* x, const void* w, const void* bias,
+                             void* out, void* partial, int M, int N, int K,
+                             int n_split, hipStream_t stream);
+void tl_gemm_tiled_partials(const void* x, const void* w, const void* bias,
+                            void* out, void* partial, int M, int N, int K,
+                            int n_split, hipStream_t stream);
 void tl_sample(const void* logits, const void* temps, const void* top_ps,
                const void* top_ks, const void* pres, const void* freqs,
                void* counts, const void* seeds, const void* ctr, void* out,
@@ -125,6 +137,51 @@ std::vector<Tensor> rmsnorm_fwd(Tensor x, c10::optional<Tensor> residual,
   return outs;
 }
 
+// Residual add + RMSNorm with x either bf16 [.., H] or the GEMM family's
+// fp32 split-K partials [n_split, .., H] (skinny_gemm_partials). mode 1 =
+// norm of the unrounded sum (rmsnorm_fwd with residual), 2 = norm of the
+// bf16-rounded sum (torch add, then rmsnorm_fwd), 3 = the rounded sum
+// alone. Returns {y, r} (mode 3: {r}).
+std::vector<Tensor> rmsnorm_add_fwd(Tensor x, Tensor residual,
+                                    c10::optional<Tensor> w, double eps,
+                                    int64_t mode) {
+  CHECK_IN(residual, torch::kBFloat16);
+  TORCH_CHECK(mode >= 1 && mode <= 3, "mode must be 1, 2 or 3");
+  const int H = residual.size(-1);
+  TORCH_CHECK(H % 8 == 0, "H must be divisible by 8");
+  TORCH_CHECK(H <= 16384, "rmsnorm supports H <= 16384");
+  const int64_t N = residual.numel() / H;
+  int n_split = 0;
+  if (x.scalar_type() == torch::kFloat) {
+    CHECK_IN(x, torch::kFloat);
+    TORCH_CHECK(x.dim() >= 2 && x.size(-1) == H &&
+                    x.numel() == x.size(0) * residual.numel(),
+                "partials must be [n_split, rows, H]");
+    n_split = (int)x.size(0);
+  } else {
+    CHECK_IN(x, torch::kBFloat16);
+    TORCH_CHECK(x.numel() == residual.numel() && x.size(-1) == H,
+                "x / residual shape mismatch");
+  }
+  auto r_out = torch::empty_like(residual);
+  Tensor y;
+  const void* wp = nullptr;
+  void* yp = nullptr;
+  if (mode != 3) {
+    TORCH_CHECK(w.has_value(), "weight required");
+    CHECK_IN(w.value(), torch::kBFloat16);
+    TORCH_CHECK(w->numel() == H, "weight size mismatch");
+    y = torch::empty_like(residual);
+    wp = w->data_ptr();
+    yp = y.data_ptr();
+  }
+  tl_rmsnorm_add_fwd(x.data_ptr(), residual.data_ptr(), wp, yp,
+                     r_out.data_ptr(), N, H, (float)eps, n_split, (int)mode,
+                     cur_stream());
+  if (mode == 3) return {r_out};
+  return {y, r_out};
+}
+
 std::vector<Tensor> rmsnorm_bwd(Tensor dy, Tensor x, Tensor w, Tensor rstd) {
   CHECK_IN(dy, torch::kBFloat16);
   CHECK_IN(x, torch::kBFloat16);
@@ -197,7 +254,7 @@ void adamw_(Tensor param, Tensor grad, Tensor m, Tensor v, double lr,
 
 Tensor decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor seq_lens,
                    double scale, int64_t n_split,
-                   c10::optional<Tensor> block_table) {
+                   c10::optional<Tensor> block_table, int64_t len_add) {
   CHECK_IN(q, torch::kBFloat16);
   CHECK_IN(k_cache, torch::kBFloat16);
   CHECK_IN(v_cache, torch::kBFloat16);
@@ -222,7 +279,7 @@ Tensor decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor seq_lens,
   if (legacy) {
     tl_decode_attn(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
                    seq_lens.data_ptr(), out.data_ptr(), B, Hq, Hkv, Smax, D,
-                   (float)scale, cur_stream());
+                   (float)scale, (int)len_add, cur_stream());
     return out;
   }
   int per_row = 0;
@@ -230,7 +287,8 @@ Tensor decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor seq_lens,
     // auto: per-ROW split from each row's own length (tl_split_for_len,
     // common.hpp) so a sequence's numerics are batch-independent; the
     // launch z-width comes from a batch-shape-free host bound on L
-    // (cache capacity), no device sync needed.
+    // (cache capacity, which bounds seq_lens + len_add too), no device
+    // sync needed.
     per_row = 1;
     const int upper = bt ? bt_stride * 128 : Smax;
     n_split = tl_split_for_len(upper);
@@ -249,7 +307,7 @@ Tensor decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor seq_lens,
   tl_decode_attn_mfma(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
                       seq_lens.data_ptr(), bt, out.data_ptr(), pp, pml, B,
                       Hq, Hkv, Smax, D, (float)scale, (int)n_split,
-                      bt_stride, per_row, cur_stream());
+                      bt_stride, per_row, (int)len_add, cur_stream());
   return out;
 }
 
@@ -310,22 +368,46 @@ std::vector<Tensor> attn_bwd(Tensor q, Tensor k, Tensor v, Tensor dout,
   return {dq, dk, dv};
 }
 
-// qkv: [T, row_stride] fused projection output (q | k | v per row).
-// Returns rotated q as a contiguous [T, Hq, D] tensor; k/v land in the
-// caches.
+// qkv: [T, row_stride] fused projection output (q | k | v per row), bf16 —
+// or the projection's fp32 split-K partials [n_split, T, row_stride]
+// (skinny_gemm_partials) with its bias passed alongside. inv_freq fp32 or
+// bf16. Returns rotated q as a contiguous [T, Hq, D] tensor; k/v land in
+// the caches.
 Tensor rope_append_(Tensor qkv, Tensor k_cache, Tensor v_cache,
                     Tensor positions, Tensor inv_freq, int64_t S,
                     int64_t Hq, int64_t Hkv,
-                    c10::optional<Tensor> block_table) {
-  CHECK_IN(qkv, torch::kBFloat16);
+                    c10::optional<Tensor> block_table,
+                    c10::optional<Tensor> bias) {
   CHECK_IN(k_cache, torch::kBFloat16);
   CHECK_IN(v_cache, torch::kBFloat16);
   CHECK_IN(positions, torch::kInt);
-  CHECK_IN(inv_freq, torch::kFloat);
+  TORCH_CHECK(inv_freq.is_cuda() && inv_freq.is_contiguous(),
+              "inv_freq must be a contiguous GPU tensor");
+  const bool inv_bf16 = inv_freq.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(inv_bf16 || inv_freq.scalar_type() == torch::kFloat,
+              "inv_freq must be fp32 or bf16");
   const int D = k_cache.size(3);
+  TORCH_CHECK(inv_freq.numel() >= D / 2, "inv_freq too short");
   const int row_stride = qkv.size(-1);
   TORCH_CHECK(row_stride == (Hq + 2 * Hkv) * D, "qkv width mismatch");
-  const int64_t T = qkv.numel() / row_stride;
+  int n_split = 0;
+  const void* bp = nullptr;
+  if (qkv.scalar_type() == torch::kFloat) {
+    CHECK_IN(qkv, torch::kFloat);
+    TORCH_CHECK(qkv.dim() >= 2, "partials must be [n_split, T, width]");
+    n_split = (int)qkv.size(0);
+    TORCH_CHECK(row_stride <= 32768, "qkv row too wide for the LDS stage");
+    if (bias.has_value()) {
+      CHECK_IN(bias.value(), torch::kBFloat16);
+      TORCH_CHECK(bias->numel() == row_stride, "bias size mismatch");
+      bp = bias->data_ptr();
+    }
+  } else {
+    CHECK_IN(qkv, torch::kBFloat16);
+    TORCH_CHECK(!bias.has_value(), "bias goes with partials only");
+  }
+  const int64_t T = qkv.numel() / row_stride / (n_split ? n_split : 1);
+  TORCH_CHECK(positions.numel() == T, "positions size mismatch");
   const int Smax = k_cache.size(2);
   TORCH_CHECK(T % S == 0, "T must be divisible by S");
   TORCH_CHECK(D % 16 == 0, "D must be divisible by 16");
@@ -340,11 +422,12 @@ Tensor rope_append_(Tensor qkv, Tensor k_cache, Tensor v_cache,
   } else {
     TORCH_CHECK(k_cache.size(0) * S == T, "cache batch mismatch");
   }
-  auto q_out = torch::empty({T, Hq, (int64_t)D}, qkv.options());
-  tl_rope_append(qkv.data_ptr(), q_out.data_ptr(), k_cache.data_ptr(),
+  auto q_out = torch::empty({T, Hq, (int64_t)D}, k_cache.options());
+  tl_rope_append(qkv.data_ptr(), bp, q_out.data_ptr(), k_cache.data_ptr(),
                  v_cache.data_ptr(), positions.data_ptr(),
                  inv_freq.data_ptr(), bt, T, row_stride, (int)S, (int)Hq,
-                 (int)Hkv, D, Smax, bt_stride, cur_stream());
+                 (int)Hkv, D, Smax, bt_stride, n_split, inv_bf16 ? 1 : 0,
+                 cur_stream());
   return q_out;
 }
 
@@ -424,6 +507,37 @@ Tensor skinny_gemm(Tensor x, Tensor w, c10::optional<Tensor> bias) {
     tl_gemm_tiled(x.data_ptr(), w.data_ptr(), bp, out.data_ptr(), pp,
                   (int)M, N, K, n_split, cur_stream());
   return out;
+}
+
+// skinny_gemm without the reduce pass: returns the fp32 split-K partials
+// [n_split, .., N] for a consumer kernel to sum (s order from 0, then
+// bias, then one bf16 rounding — exactly what the reduce kernels do), so
+// bias is NOT applied. When the policy gives n_split == 1 there is nothing
+// to hand out and the bf16 output comes back as from skinny_gemm, bias
+// included.
+Tensor skinny_gemm_partials(Tensor x, Tensor w, c10::optional<Tensor> bias) {
+  CHECK_IN(x, torch::kBFloat16);
+  CHECK_IN(w, torch::kBFloat16);
+  const int K = x.size(-1);
+  const int64_t M = x.numel() / K;
+  const int N = w.size(0);
+  TORCH_CHECK(w.size(1) == K, "K mismatch");
+  TORCH_CHECK(K % 32 == 0 && N % 64 == 0, "unsupported shape");
+  const int n_split = gemm_n_split(N, K);
+  if (n_split == 1) return skinny_gemm(x, w, bias);
+  auto sizes = x.sizes().vec();
+  sizes.back() = N;
+  sizes.insert(sizes.begin(), n_split);
+  auto partial = torch::empty(sizes, x.options().dtype(torch::kFloat));
+  if (M <= 64)
+    tl_skinny_gemm_partials(x.data_ptr(), w.data_ptr(), nullptr, nullptr,
+                            partial.data_ptr(), (int)M, N, K, n_split,
+                            cur_stream());
+  else
+    tl_gemm_tiled_partials(x.data_ptr(), w.data_ptr(), nullptr, nullptr,
+                           partial.data_ptr(), (int)M, N, K, n_split,
+                           cur_stream());
+  return partial;
 }
 
 // Split-K policy of the MXFP4 weight GEMM (mxfp4_gemm.hip). (N,K)-pure like
@@ -644,6 +758,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "fused RoPE + KV-cache append from fused-QKV rows");
   mod.def("swiglu_fused", &swiglu_fused, "silu-mul on fused [.,2I] rows");
   mod.def("skinny_gemm", &skinny_gemm, "decode-M GEMM: x @ W^T + bias");
+  mod.def("skinny_gemm_partials", &skinny_gemm_partials,
+          "decode-M GEMM handing out its fp32 split-K partials");
+  mod.def("rmsnorm_add_fwd", &rmsnorm_add_fwd,
+          "residual add + RMSNorm from bf16 or split-K partials");
   mod.def("rmsnorm_fwd", &rmsnorm_fwd, "fused RMSNorm fwd (+residual)");
   mod.def("rmsnorm_bwd", &rmsnorm_bwd, "RMSNorm bwd");
   mod.def("rope_", &rope_, "in-place RoPE apply");

@@ -85,6 +85,54 @@ __host__ __device__ inline int64_t cdiv64(int64_t a, int64_t b) {
 }
 
 // ---------------------------------------------------------------------------
+// Split-K partial consumers (rmsnorm.hip, rope_append.hip). The GEMM family
+// can hand its fp32 partials [n_split, rows, N] to the next kernel instead
+// of reducing them itself; the consumer must then reproduce the reduce
+// kernels' sum bit for bit: from 0.f, ascending s.
+//
+// acc[v][0..8) = sum_s p[v][s * split_stride + 0..8) for NV 8-column groups
+// at once (p[v] 16-byte aligned). Each batch fetches CH splits of all NV
+// groups before the first add — NV*CH*2 16-byte loads in flight — because
+// these kernels run one small block per row and would otherwise wait out
+// one memory latency per split. A short last batch re-reads the final
+// split (clamped, always in bounds) and skips its adds.
+// ---------------------------------------------------------------------------
+template <int NV, int CH>
+DEVINLINE void sum_partials8(const float* (&p)[NV],
+                             int64_t split_stride, int n_split,
+                             float (&acc)[NV][8]) {
+#pragma unroll
+  for (int v = 0; v < NV; ++v)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[v][j] = 0.f;
+  for (int s0 = 0; s0 < n_split; s0 += CH) {
+    f32x4_u buf[NV][CH][2];
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+      for (int k = 0; k < CH; ++k) {
+        const int s = min(s0 + k, n_split - 1);
+        const float4* q =
+            reinterpret_cast<const float4*>(p[v] + s * split_stride);
+        buf[v][k][0].f4 = q[0];
+        buf[v][k][1].f4 = q[1];
+      }
+#pragma unroll
+    for (int k = 0; k < CH; ++k) {
+      if (s0 + k < n_split) {
+#pragma unroll
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            acc[v][j] += buf[v][k][0].f[j];
+            acc[v][4 + j] += buf[v][k][1].f[j];
+          }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // ds_read_b64_tr_b16 (gfx950 LDS transpose read) — no clang builtin; inline
 // asm. Measured semantics (scripts/tr16_probe.hip): within each 16-lane
 // group, the 16 lanes' 8-byte reads form a 64-element vector V (in lane

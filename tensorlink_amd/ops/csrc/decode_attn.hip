@@ -31,7 +31,7 @@ __global__ __launch_bounds__(BLOCK) void decode_attn_kernel(
     const bf16* __restrict__ v_cache,  // [B, Hkv, Smax, D]
     const int* __restrict__ seq_lens,  // [B]
     bf16* __restrict__ out,            // [B, Hq, D]
-    int Hq, int Hkv, int Smax, float scale) {
+    int Hq, int Hkv, int Smax, float scale, int len_add) {
   constexpr int EPL = D / LPK;  // elements per lane (16 at D=128)
   const int b = blockIdx.x;
   const int hkv = blockIdx.y;
@@ -39,7 +39,7 @@ __global__ __launch_bounds__(BLOCK) void decode_attn_kernel(
   const int g0 = blockIdx.z * GMAX;          // first query head in group
   const int gq = min(GMAX, G - g0);          // heads this block handles
   const int h0 = hkv * G + g0;               // absolute first q head
-  const int L = seq_lens[b];
+  const int L = seq_lens[b] + len_add;
 
   const int lane = threadIdx.x & (WAVE_SIZE - 1);
   const int wave = threadIdx.x / WAVE_SIZE;
@@ -177,7 +177,8 @@ extern "C" {
 
 void tl_decode_attn(const void* q, const void* k_cache, const void* v_cache,
                     const void* seq_lens, void* out, int B, int Hq, int Hkv,
-                    int Smax, int D, float scale, hipStream_t stream) {
+                    int Smax, int D, float scale, int len_add,
+                    hipStream_t stream) {
   const int G = Hq / Hkv;
   // One block covers up to GMAX query heads of one kv head, so the K/V
   // slab is streamed once per GROUP of query heads (GQA bandwidth saving).
@@ -191,7 +192,7 @@ void tl_decode_attn(const void* q, const void* k_cache, const void* v_cache,
   hipLaunchKernelGGL((decode_attn_kernel<DD, GG>), grid, block, 0, stream, \
                      (const bf16*)q, (const bf16*)k_cache,                 \
                      (const bf16*)v_cache, (const int*)seq_lens,           \
-                     (bf16*)out, Hq, Hkv, Smax, scale)
+                     (bf16*)out, Hq, Hkv, Smax, scale, len_add)
   if (D == 128) {
     if (gmax == 2) LAUNCH(128, 2);
     else if (gmax == 4) LAUNCH(128, 4);

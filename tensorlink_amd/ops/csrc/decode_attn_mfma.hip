@@ -44,7 +44,7 @@ __global__ __launch_bounds__(BLOCK) void decode_attn_mfma_kernel(
     float* __restrict__ partial,       // [B, Hq, SPLIT, D]
     float* __restrict__ partial_ml,    // [B, Hq, SPLIT, 2]
     int Hq, int Hkv, int Smax, float scale, int n_split, int bt_stride,
-    int per_row) {
+    int per_row, int len_add) {
   constexpr int KCH = D / 32;        // MFMA k-chunks for QK^T
   constexpr int NS = D / 16;         // PV output col tiles
   const int b = blockIdx.x;
@@ -52,7 +52,9 @@ __global__ __launch_bounds__(BLOCK) void decode_attn_mfma_kernel(
   const int split = blockIdx.z;
   const int G = Hq / Hkv;
   const int h0 = hkv * G;
-  const int L = seq_lens[b];
+  // len_add: tokens the caller appended this step but has not yet counted
+  // in seq_lens (decode passes 1 instead of a seq_lens + 1 tensor op)
+  const int L = seq_lens[b] + len_add;
 
   // per_row: this ROW's split count comes from its own length (batch
   // composition must not change a row's accumulation — exact-greedy
@@ -267,11 +269,11 @@ template <int D>
 __global__ __launch_bounds__(128) void decode_attn_combine_kernel(
     const float* __restrict__ partial, const float* __restrict__ partial_ml,
     const int* __restrict__ seq_lens, bf16* __restrict__ out, int Hq,
-    int n_split, int per_row) {
+    int n_split, int per_row, int len_add) {
   const int bh = blockIdx.x;                    // b * Hq + h
   const int d = threadIdx.x;                    // [0, D)
   const int ns_row =
-      per_row ? tl_split_for_len(seq_lens[bh / Hq]) : n_split;
+      per_row ? tl_split_for_len(seq_lens[bh / Hq] + len_add) : n_split;
   __shared__ float sm[64], sl[64];
   if (threadIdx.x < ns_row) {
     sm[threadIdx.x] = partial_ml[((int64_t)bh * n_split + threadIdx.x) * 2];
@@ -300,7 +302,8 @@ void tl_decode_attn_mfma(const void* q, const void* k_cache,
                          const void* block_table, void* out,
                          void* partial, void* partial_ml, int B, int Hq,
                          int Hkv, int Smax, int D, float scale, int n_split,
-                         int bt_stride, int per_row, hipStream_t stream) {
+                         int bt_stride, int per_row, int len_add,
+                         hipStream_t stream) {
   dim3 grid(B, Hkv, n_split), block(BLOCK);
 #define LAUNCH(DD, SM, PG)                                                   \
   hipLaunchKernelGGL((decode_attn_mfma_kernel<DD, SM, PG>), grid, block, 0,  \
@@ -308,7 +311,7 @@ void tl_decode_attn_mfma(const void* q, const void* k_cache,
                      (const bf16*)v_cache, (const int*)seq_lens,             \
                      (const int*)block_table, (bf16*)out,                    \
                      (float*)partial, (float*)partial_ml, Hq, Hkv, Smax,     \
-                     scale, n_split, bt_stride, per_row)
+                     scale, n_split, bt_stride, per_row, len_add)
 #define PICK(DD)                                                             \
   do {                                                                       \
     if (block_table) {                                                       \
@@ -327,12 +330,12 @@ void tl_decode_attn_mfma(const void* q, const void* k_cache,
       hipLaunchKernelGGL((decode_attn_combine_kernel<128>), cgrid, cblock, 0,
                          stream, (const float*)partial,
                          (const float*)partial_ml, (const int*)seq_lens,
-                         (bf16*)out, Hq, n_split, per_row);
+                         (bf16*)out, Hq, n_split, per_row, len_add);
     else
       hipLaunchKernelGGL((decode_attn_combine_kernel<64>), cgrid, cblock, 0,
                          stream, (const float*)partial,
                          (const float*)partial_ml, (const int*)seq_lens,
-                         (bf16*)out, Hq, n_split, per_row);
+                         (bf16*)out, Hq, n_split, per_row, len_add);
   }
 }
 

@@ -326,14 +326,11 @@ __global__ void gemm_reduce_kernel(const float* __restrict__ partial,
   out[i] = f2bf(acc);
 }
 
-}  // namespace
-
-extern "C" {
-
-// partial: scratch [n_split * M * N] floats (only read when n_split > 1).
-void tl_gemm_tiled(const void* x, const void* w, const void* bias, void* out,
-                   void* partial, int M, int N, int K, int n_split,
-                   hipStream_t stream) {
+// reduce == 0 leaves the fp32 partials for the consumer (see
+// skinny_gemm.hip).
+void tiled_launch(const void* x, const void* w, const void* bias, void* out,
+                  void* partial, int M, int N, int K, int n_split,
+                  int reduce, hipStream_t stream) {
   const int m_tiles = (M + 15) / 16;
   const int split = n_split > 1 ? 1 : 0;
   // very-wide-N shapes (lm_head) take the 256x256 8-wave kernel; at
@@ -376,7 +373,7 @@ void tl_gemm_tiled(const void* x, const void* w, const void* bias, void* out,
   else DISPATCH(16);
 #undef DISPATCH
   }
-  if (split) {
+  if (split && reduce) {
     const int64_t MN = (int64_t)M * N;
     dim3 rgrid((uint32_t)((MN + 255) / 256)), rblock(256);
     if (bias)
@@ -388,6 +385,23 @@ void tl_gemm_tiled(const void* x, const void* w, const void* bias, void* out,
                          (const float*)partial, nullptr, (bf16*)out, MN, N,
                          n_split);
   }
+}
+
+}  // namespace
+
+extern "C" {
+
+// partial: scratch [n_split * M * N] floats (only read when n_split > 1).
+void tl_gemm_tiled(const void* x, const void* w, const void* bias, void* out,
+                   void* partial, int M, int N, int K, int n_split,
+                   hipStream_t stream) {
+  tiled_launch(x, w, bias, out, partial, M, N, K, n_split, 1, stream);
+}
+
+void tl_gemm_tiled_partials(const void* x, const void* w, const void* bias,
+                            void* out, void* partial, int M, int N, int K,
+                            int n_split, hipStream_t stream) {
+  tiled_launch(x, w, bias, out, partial, M, N, K, n_split, 0, stream);
 }
 
 }  // extern "C"

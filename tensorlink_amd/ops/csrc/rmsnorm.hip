@@ -17,16 +17,42 @@ constexpr int BLOCK = 256;
 constexpr int NW = BLOCK / WAVE_SIZE;
 
 // Forward: one block per row, ITERS*BLOCK*8 >= H.
-// RES: 0 = plain, 1 = fused residual add (writes r = x + residual).
-template <int ITERS, int RES>
+// RES: 0 = plain norm of x.
+//      1 = fused residual add ("mode A"): f = x + residual in fp32,
+//          r_out = bf16(f), the norm uses the UNROUNDED f.
+//      2 = add, then plain norm ("mode B"): r_out = bf16(x + residual), the
+//          norm uses the ROUNDED r_out — what a separate bf16 add kernel
+//          followed by the RES=0 norm computes.
+//      3 = mode B's add alone: writes r_out, no norm.
+// PART: x is the fp32 split-K partial tensor [n_split, rows, H] of the GEMM
+// family (split_stride = rows*H) instead of bf16 [rows, H]; the element is
+// bf16(sum_s partial[s]) summed from 0 in s order — the value the GEMM's
+// own reduce kernel writes.
+template <int ITERS, int RES, int PART>
 __global__ __launch_bounds__(BLOCK) void rmsnorm_fwd_kernel(
-    const bf16* __restrict__ x, const bf16* __restrict__ residual,
+    const void* __restrict__ x_, const bf16* __restrict__ residual,
     const bf16* __restrict__ w, bf16* __restrict__ y, bf16* __restrict__ r_out,
-    float* __restrict__ rstd_out, int H, float eps) {
+    float* __restrict__ rstd_out, int H, float eps, int n_split,
+    int64_t split_stride) {
   __shared__ float lds[NW];
   const int64_t row = blockIdx.x;
-  const bf16* xrow = x + row * H;
+  const bf16* xrow = PART ? nullptr : (const bf16*)x_ + row * H;
+  const float* prow = PART ? (const float*)x_ + row * H : nullptr;
   const bf16* rrow = RES ? residual + row * H : nullptr;
+
+  // partials: sum every group this thread owns up front (idle lanes of a
+  // ragged last iteration re-read column 0 and drop the result)
+  constexpr int CH = ITERS <= 2 ? 8 : ITERS <= 4 ? 4 : 2;
+  float psum[PART ? ITERS : 1][8];
+  if constexpr (PART) {
+    const float* pp[ITERS];
+#pragma unroll
+    for (int it = 0; it < ITERS; ++it) {
+      const int base = (it * BLOCK + threadIdx.x) * 8;
+      pp[it] = prow + (base < H ? base : 0);
+    }
+    sum_partials8<ITERS, CH>(pp, split_stride, n_split, psum);
+  }
 
   float vals[ITERS][8];
   float sumsq = 0.f;
@@ -34,18 +60,24 @@ __global__ __launch_bounds__(BLOCK) void rmsnorm_fwd_kernel(
   for (int it = 0; it < ITERS; ++it) {
     const int base = (it * BLOCK + threadIdx.x) * 8;
     if (base < H) {
-      bf16x8 vx = *reinterpret_cast<const bf16x8*>(xrow + base);
+      bf16x8 vx;
+      if constexpr (PART) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) vx.v[j] = f2bf(psum[it][j]);
+      } else {
+        vx = *reinterpret_cast<const bf16x8*>(xrow + base);
+      }
       if (RES) {
         bf16x8 vr = *reinterpret_cast<const bf16x8*>(rrow + base);
+        bf16x8 out;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           float f = bf2f(vx.v[j]) + bf2f(vr.v[j]);
+          out.v[j] = f2bf(f);
+          if (RES >= 2) f = bf2f(out.v[j]);
           vals[it][j] = f;
           sumsq += f * f;
         }
-        bf16x8 out;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) out.v[j] = f2bf(vals[it][j]);
         *reinterpret_cast<bf16x8*>(r_out + row * H + base) = out;
       } else {
 #pragma unroll
@@ -60,6 +92,7 @@ __global__ __launch_bounds__(BLOCK) void rmsnorm_fwd_kernel(
       for (int j = 0; j < 8; ++j) vals[it][j] = 0.f;
     }
   }
+  if (RES == 3) return;
 
   const float total = block_reduce_sum<NW>(sumsq, lds);
   const float rstd = rsqrtf(total / H + eps);
@@ -156,16 +189,18 @@ __global__ void reduce_partials_kernel(const float* __restrict__ partials,
   out[i] = f2bf(acc);
 }
 
-template <int RES>
-void launch_fwd(const bf16* x, const bf16* res, const bf16* w, bf16* y,
+template <int RES, int PART>
+void launch_fwd(const void* x, const bf16* res, const bf16* w, bf16* y,
                 bf16* r_out, float* rstd, int64_t N, int H, float eps,
-                hipStream_t s) {
+                int n_split, hipStream_t s) {
   dim3 grid((uint32_t)N), block(BLOCK);
   const int iters = cdiv(H, BLOCK * 8);
-#define CASE(I)                                                            \
-  case I:                                                                  \
-    hipLaunchKernelGGL((rmsnorm_fwd_kernel<I, RES>), grid, block, 0, s, x, \
-                       res, w, y, r_out, rstd, H, eps);                    \
+  const int64_t split_stride = N * H;
+#define CASE(I)                                                              \
+  case I:                                                                    \
+    hipLaunchKernelGGL((rmsnorm_fwd_kernel<I, RES, PART>), grid, block, 0,   \
+                       s, x, res, w, y, r_out, rstd, H, eps, n_split,        \
+                       split_stride);                                        \
     break;
   switch (iters) {
     CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
@@ -182,11 +217,33 @@ void tl_rmsnorm_fwd(const void* x, const void* residual, const void* w,
                     void* y, void* r_out, void* rstd, int64_t N, int H,
                     float eps, hipStream_t stream) {
   if (residual)
-    launch_fwd<1>((const bf16*)x, (const bf16*)residual, (const bf16*)w,
-                  (bf16*)y, (bf16*)r_out, (float*)rstd, N, H, eps, stream);
+    launch_fwd<1, 0>(x, (const bf16*)residual, (const bf16*)w, (bf16*)y,
+                     (bf16*)r_out, (float*)rstd, N, H, eps, 1, stream);
   else
-    launch_fwd<0>((const bf16*)x, nullptr, (const bf16*)w, (bf16*)y, nullptr,
-                  (float*)rstd, N, H, eps, stream);
+    launch_fwd<0, 0>(x, nullptr, (const bf16*)w, (bf16*)y, nullptr,
+                     (float*)rstd, N, H, eps, 1, stream);
+}
+
+// Residual add + norm with x as bf16 [N, H] (n_split == 0) or as the GEMM
+// family's fp32 partials [n_split, N, H]. mode 1/2/3 = the kernel's RES
+// (A: norm of the unrounded sum; B: norm of the rounded sum; 3: sum only,
+// y and w unused).
+void tl_rmsnorm_add_fwd(const void* x, const void* residual, const void* w,
+                        void* y, void* r_out, int64_t N, int H, float eps,
+                        int n_split, int mode, hipStream_t stream) {
+#define GO(R, P)                                                          \
+  launch_fwd<R, P>(x, (const bf16*)residual, (const bf16*)w, (bf16*)y,    \
+                   (bf16*)r_out, nullptr, N, H, eps, n_split, stream)
+  if (n_split > 0) {
+    if (mode == 1) GO(1, 1);
+    else if (mode == 2) GO(2, 1);
+    else GO(3, 1);
+  } else {
+    if (mode == 1) GO(1, 0);
+    else if (mode == 2) GO(2, 0);
+    else GO(3, 0);
+  }
+#undef GO
 }
 
 // dw_partial must hold [n_blocks, H] floats; returns via dx, dw.

@@ -140,14 +140,11 @@ __global__ void skinny_reduce_kernel(const float* __restrict__ partial,
   out[i] = f2bf(acc);
 }
 
-}  // namespace
-
-extern "C" {
-
-// partial: scratch [n_split * M * N] floats (only read when n_split > 1).
-void tl_skinny_gemm(const void* x, const void* w, const void* bias,
-                    void* out, void* partial, int M, int N, int K,
-                    int n_split, hipStream_t stream) {
+// reduce == 0 leaves the fp32 partials for the consumer to sum (in s
+// order, then bias) — rope_append / rmsnorm read them directly.
+void skinny_launch(const void* x, const void* w, const void* bias,
+                   void* out, void* partial, int M, int N, int K,
+                   int n_split, int reduce, hipStream_t stream) {
   const int m_tiles = (M + 15) / 16;
   const int split = n_split > 1 ? 1 : 0;
   dim3 grid(N / 64, n_split), block(BLOCK);
@@ -174,7 +171,7 @@ void tl_skinny_gemm(const void* x, const void* w, const void* bias,
   else if (m_tiles <= 8) DISPATCH(8);
   else DISPATCH(16);
 #undef DISPATCH
-  if (split) {
+  if (split && reduce) {
     const int64_t MN = (int64_t)M * N;
     dim3 rgrid((uint32_t)((MN + 255) / 256)), rblock(256);
     if (bias)
@@ -186,6 +183,26 @@ void tl_skinny_gemm(const void* x, const void* w, const void* bias,
                          (const float*)partial, nullptr, (bf16*)out, MN, N,
                          n_split);
   }
+}
+
+}  // namespace
+
+extern "C" {
+
+// partial: scratch [n_split * M * N] floats (only read when n_split > 1).
+void tl_skinny_gemm(const void* x, const void* w, const void* bias,
+                    void* out, void* partial, int M, int N, int K,
+                    int n_split, hipStream_t stream) {
+  skinny_launch(x, w, bias, out, partial, M, N, K, n_split, 1, stream);
+}
+
+// Same main kernel, no reduce: with n_split > 1 only `partial`
+// [n_split, M, N] is written (bias not applied); with n_split == 1 this is
+// tl_skinny_gemm.
+void tl_skinny_gemm_partials(const void* x, const void* w, const void* bias,
+                             void* out, void* partial, int M, int N, int K,
+                             int n_split, hipStream_t stream) {
+  skinny_launch(x, w, bias, out, partial, M, N, K, n_split, 0, stream);
 }
 
 }  // extern "C"
