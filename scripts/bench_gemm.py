@@ -28,6 +28,9 @@ def timeit(fn, iters=50):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--csv", default=None)
+    ap.add_argument("--colbal", action="store_true",
+                    help="only the shapes the column-balanced kernel "
+                         "serves (gate_up at M=128/256/512, lm_head)")
     args = ap.parse_args()
     C = ops._require_ext()
     rows = []
@@ -47,6 +50,11 @@ def main():
         (16, 3584, 3584, "o_m16"),
         (1, 4608, 3584, "qkv_m1"),
     ]
+    if args.colbal:
+        shapes = [(128, 37888, 3584, "gate_up_m128"),
+                  (256, 37888, 3584, "gate_up"),
+                  (512, 37888, 3584, "gate_up_m512"),
+                  (256, 151936, 3584, "lm_head")]
     for M, N, K, name in shapes:
         x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
         w = torch.randn(N, K, device="cuda", dtype=torch.bfloat16) / K ** 0.5
@@ -61,12 +69,28 @@ def main():
                 f"lib {t_lib:7.1f}us ({wb / t_lib * 1e3:5.2f} TB/s)  "
                 f"tl {t_tl:7.1f}us ({wb / t_tl * 1e3:5.2f} TB/s)  "
                 f"maxerr {err:.3f}")
+        t_cb = t_cbf = t_chain = float("nan")
+        if M > 64 and C.gemm_n_split(N, K) == 1:
+            # column-balanced one-pass kernel, alone and with SwiGLU on
+            # the accumulators, against library GEMM + swiglu_fused
+            t_cb = timeit(lambda: C.gemm_colbal(x, w))
+            t_cbf = timeit(lambda: C.gemm_colbal_swiglu(x, w))
+            t_chain = timeit(lambda: C.swiglu_fused(
+                torch.nn.functional.linear(x, w)))
+            same = torch.equal(C.gemm_colbal(x, w),
+                               C.skinny_gemm(x, w, None))
+            fl = 2.0 * M * N * K / 1e12
+            line += (f"  colbal {t_cb:7.1f}us ({wb / t_cb * 1e3:5.2f} TB/s "
+                     f"{fl / t_cb * 1e6:5.0f} TF, bits==tl {same})  "
+                     f"colbal+swiglu {t_cbf:7.1f}us  "
+                     f"lib+swiglu {t_chain:7.1f}us")
         print(line, flush=True)
-        rows.append((name, M, N, K, t_lib, t_tl, err))
+        rows.append((name, M, N, K, t_lib, t_tl, err, t_cb, t_cbf, t_chain))
     if args.csv:
         os.makedirs(os.path.dirname(args.csv), exist_ok=True)
         with open(args.csv, "w") as f:
-            f.write("name,M,N,K,lib_us,tl_us,maxerr\n")
+            f.write("name,M,N,K,lib_us,tl_us,maxerr,colbal_us,"
+                    "colbal_swiglu_us,lib_swiglu_us\n")
             for r in rows:
                 f.write(",".join(str(v) for v in r) + "\n")
 

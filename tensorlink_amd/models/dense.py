@@ -237,14 +237,22 @@ class MLP(nn.Module):
         self.down_proj = TLLinear(i, h, bias=False)
 
     def forward(self, x, fuse: bool = False):
-        gu = self.gate_up_proj(x)
-        if torch.is_grad_enabled() and gu.requires_grad:
-            gate, up = gu.split([self.inter, self.inter], dim=-1)
-            return self.down_proj(ops.swiglu(gate.contiguous(),
-                                             up.contiguous()))
+        if (type(self.gate_up_proj) is TLLinear and not
+                torch.is_grad_enabled()):
+            # inference on a plain bf16 projection: at decode batch sizes
+            # one kernel computes gate_up and applies SwiGLU to the
+            # accumulators; elsewhere this is swiglu_fused(linear(x))
+            act = ops.gate_up_swiglu(x, self.gate_up_proj.weight)
+        else:
+            gu = self.gate_up_proj(x)
+            if torch.is_grad_enabled() and gu.requires_grad:
+                gate, up = gu.split([self.inter, self.inter], dim=-1)
+                return self.down_proj(ops.swiglu(gate.contiguous(),
+                                                 up.contiguous()))
+            act = ops.swiglu_fused(gu)
         if fuse:    # may return ops.Partials (see _project)
-            return _project(self.down_proj, ops.swiglu_fused(gu))
-        return self.down_proj(ops.swiglu_fused(gu))
+            return _project(self.down_proj, act)
+        return self.down_proj(act)
 
 
 class MoEMLP(nn.Module):

@@ -432,14 +432,16 @@ gemm_dispatch_count = 0
 
 # (N,K)-pure shape classes; TL_GEMM_LIB_CLASSES routes whole classes to
 # hipBLASLt for in-pipeline A/B (a class flips for ALL M at once, so the
-# bitwise M-independence guarantee is preserved per process)
-# default: the gateup class (16k <= N < 64k) routes to hipBLASLt — the
-# BN=64/256 custom structures both lose ~40 us there in-pipeline
-# (profiles/gemm_family_ab.md); all other classes are custom, keeping
-# bitwise M-independence by construction where the tests assert it
+# bitwise M-independence guarantee is preserved per process).
+# default: empty — every class runs the hand-written family. The gateup
+# class (16k <= N < 64k), where the BN=64/256 structures lost ~40 us to
+# the library (profiles/gemm_family_ab.md), takes the column-balanced
+# one-pass kernel (gemm_colbal.hip) at 65 <= M <= GEMM_M_MAX: one
+# workgroup per CU, 9-10 column tiles each, same K chain as the family and
+# so the same bits as skinny_gemm at every M (profiles/gemm_colbal.md).
+# TL_GEMM_LIB_CLASSES=gateup restores the library route.
 _LIB_CLASSES = frozenset(
-    c for c in _os.environ.get("TL_GEMM_LIB_CLASSES",
-                               "gateup").split(",") if c)
+    c for c in _os.environ.get("TL_GEMM_LIB_CLASSES", "").split(",") if c)
 
 
 def _gemm_class(N: int, K: int) -> str:
@@ -457,24 +459,65 @@ def _use_tl_gemm(M: int, N: int, K: int) -> bool:
             and _gemm_class(N, K) not in _LIB_CLASSES)
 
 
+_n_split_cache = {}
+
+
+def _use_colbal(M: int, N: int, K: int) -> bool:
+    """The column-balanced kernel's domain: the gateup class at 65 <= M <=
+    GEMM_M_MAX where the family's policy does not split K (always, at the
+    default split target). TL_NO_COLBAL=1 keeps the class on skinny_gemm
+    (same bits) for A/B runs and tests; read per call."""
+    if not (65 <= M and _use_tl_gemm(M, N, K)
+            and _gemm_class(N, K) == "gateup"
+            and not _os.environ.get("TL_NO_COLBAL")):
+        return False
+    ns = _n_split_cache.get((N, K))
+    if ns is None:
+        ns = _n_split_cache[(N, K)] = _require_ext().gemm_n_split(N, K)
+    return ns == 1
+
+
+def _family_input(x: torch.Tensor) -> bool:
+    return (x.is_cuda and not torch.is_grad_enabled()
+            and x.dtype == torch.bfloat16
+            and not _os.environ.get("TL_NO_SKINNY"))
+
+
 def linear(x: torch.Tensor, weight: torch.Tensor,
            bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x @ W^T + bias. Serving-M shapes route to the hand-written MFMA
-    family (skinny_gemm.hip / gemm_tiled.hip); large prefill M and
-    training go to torch/hipBLASLt."""
+    family (skinny_gemm.hip / gemm_tiled.hip / gemm_colbal.hip); large
+    prefill M and training go to torch/hipBLASLt."""
     global gemm_dispatch_count
-    if (x.is_cuda and not torch.is_grad_enabled()
-            and x.dtype == torch.bfloat16
-            and not _os.environ.get("TL_NO_SKINNY")):
+    if _family_input(x):
         K = x.shape[-1]
         M = x.numel() // K
         N = weight.shape[0]
+        if bias is None and _use_colbal(M, N, K):
+            gemm_dispatch_count += 1
+            return _require_ext().gemm_colbal(x.contiguous(), weight)
         if _use_tl_gemm(M, N, K):
             gemm_dispatch_count += 1
             return _require_ext().skinny_gemm(
                 x.contiguous(), weight,
                 bias.to(torch.bfloat16) if bias is not None else None)
     return torch.nn.functional.linear(x, weight, bias)
+
+
+def gate_up_swiglu(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """swiglu_fused(linear(x, weight)) for a fused gate_up weight [2I, K]
+    (gate rows, then up rows), [.., I]. In the column-balanced kernel's
+    domain the activation is applied to the accumulators (gemm_colbal.hip,
+    fused variant): no [M, 2I] round trip, no second kernel, same bits.
+    TL_NO_GATEUP_FUSION=1 keeps the two-kernel chain (read per call)."""
+    global gemm_dispatch_count
+    if _family_input(x) and not _os.environ.get("TL_NO_GATEUP_FUSION"):
+        K = x.shape[-1]
+        M = x.numel() // K
+        if _use_colbal(M, weight.shape[0], K):
+            gemm_dispatch_count += 1
+            return _require_ext().gemm_colbal_swiglu(x.contiguous(), weight)
+    return swiglu_fused(linear(x, weight))
 
 
 def decode_fusion_enabled() -> bool:

@@ -61,6 +61,8 @@ void tl_skinny_gemm_partials(const void* x, const void* w, const void* bias,
 void tl_gemm_tiled_partials(const void* x, const void* w, const void* bias,
                             void* out, void* partial, int M, int N, int K,
                             int n_split, hipStream_t stream);
+void tl_gemm_colbal(const void* x, const void* w, void* out, int M, int N,
+                    int K, int n_blocks, int fused, hipStream_t stream);
 void tl_sample(const void* logits, const void* temps, const void* top_ps,
                const void* top_ks, const void* pres, const void* freqs,
                void* counts, const void* seeds, const void* ctr, void* out,
@@ -540,6 +542,60 @@ Tensor skinny_gemm_partials(Tensor x, Tensor w, c10::optional<Tensor> bias) {
   return partial;
 }
 
+// CU count of a device, read once: the column-balanced GEMM launches one
+// workgroup per CU (gemm_colbal.hip).
+static int device_cu_count(int dev) {
+  static int cus[64] = {0};
+  TORCH_CHECK(dev >= 0 && dev < 64, "device index out of range");
+  if (cus[dev] == 0) {
+    int n = 0;
+    TORCH_CHECK(hipDeviceGetAttribute(
+                    &n, hipDeviceAttributeMultiprocessorCount, dev) ==
+                        hipSuccess && n > 0,
+                "cannot read the CU count");
+    cus[dev] = n;
+  }
+  return cus[dev];
+}
+
+// Column-balanced one-pass GEMM (gemm_colbal.hip): x @ W^T for the wide
+// shapes where the policy gives n_split == 1, bitwise equal to skinny_gemm
+// there. fused: W is [2I, K] (gate rows, then up rows) and the result is
+// swiglu_fused(x @ W^T), [.., I]. n_blocks (workgroups per 256-row block)
+// defaults to the CU count; the bits do not depend on it, tests use it to
+// force uneven and multi-pass column ranges.
+static Tensor gemm_colbal_impl(Tensor x, Tensor w, int64_t n_blocks,
+                               bool fused) {
+  CHECK_IN(x, torch::kBFloat16);
+  CHECK_IN(w, torch::kBFloat16);
+  const int K = x.size(-1);
+  const int64_t M = x.numel() / K;
+  const int N = w.size(0);
+  TORCH_CHECK(w.dim() == 2 && w.size(1) == K, "K mismatch");
+  TORCH_CHECK(K % 32 == 0 && K >= 32 && M >= 1 && M < (1 << 24),
+              "unsupported shape");
+  TORCH_CHECK(N % (fused ? 32 : 16) == 0 && N > 0, "unsupported width");
+  TORCH_CHECK(gemm_n_split(N, K) == 1,
+              "gemm_colbal serves only shapes the policy does not split");
+  if (n_blocks <= 0) n_blocks = device_cu_count(x.get_device());
+  TORCH_CHECK(n_blocks <= 65535, "n_blocks too large");
+  const int NO = fused ? N / 2 : N;
+  auto sizes = x.sizes().vec();
+  sizes.back() = NO;
+  auto out = torch::empty(sizes, x.options());
+  tl_gemm_colbal(x.data_ptr(), w.data_ptr(), out.data_ptr(), (int)M, NO, K,
+                 (int)n_blocks, fused ? 1 : 0, cur_stream());
+  return out;
+}
+
+Tensor gemm_colbal(Tensor x, Tensor w, int64_t n_blocks) {
+  return gemm_colbal_impl(x, w, n_blocks, false);
+}
+
+Tensor gemm_colbal_swiglu(Tensor x, Tensor w_gate_up, int64_t n_blocks) {
+  return gemm_colbal_impl(x, w_gate_up, n_blocks, true);
+}
+
 // Split-K policy of the MXFP4 weight GEMM (mxfp4_gemm.hip). (N,K)-pure like
 // gemm_n_split, but counted in the kernel's 128-k steps: a column's packed
 // bytes are 4x fewer than bf16, so a split must keep >= 2 steps.
@@ -758,6 +814,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "fused RoPE + KV-cache append from fused-QKV rows");
   mod.def("swiglu_fused", &swiglu_fused, "silu-mul on fused [.,2I] rows");
   mod.def("skinny_gemm", &skinny_gemm, "decode-M GEMM: x @ W^T + bias");
+  mod.def("gemm_n_split", &gemm_n_split,
+          "split-K count the GEMM family's (N,K)-only policy gives");
+  mod.def("gemm_colbal", &gemm_colbal,
+          "column-balanced one-pass GEMM: x @ W^T (n_split == 1 shapes)",
+          py::arg("x"), py::arg("w"), py::arg("n_blocks") = 0);
+  mod.def("gemm_colbal_swiglu", &gemm_colbal_swiglu,
+          "column-balanced gate_up GEMM with SwiGLU on the accumulators",
+          py::arg("x"), py::arg("w_gate_up"), py::arg("n_blocks") = 0);
   mod.def("skinny_gemm_partials", &skinny_gemm_partials,
           "decode-M GEMM handing out its fp32 split-K partials");
   mod.def("rmsnorm_add_fwd", &rmsnorm_add_fwd,

@@ -6,12 +6,11 @@
 // Flat over n elements, bf16x8 vectorized (n % 8 == 0, wrapper pads).
 
 #include "common.hpp"
+#include "swiglu_common.hpp"
 
 namespace {
 
 constexpr int BLOCK = 256;
-
-DEVINLINE float silu(float x) { return x / (1.f + __expf(-x)); }
 
 __global__ __launch_bounds__(BLOCK) void swiglu_fwd_kernel(
     const bf16* __restrict__ gate, const bf16* __restrict__ up,
@@ -23,7 +22,7 @@ __global__ __launch_bounds__(BLOCK) void swiglu_fwd_kernel(
   bf16x8 o;
 #pragma unroll
   for (int j = 0; j < 8; ++j)
-    o.v[j] = f2bf(silu(bf2f(g.v[j])) * bf2f(u.v[j]));
+    o.v[j] = swiglu_bf16(g.v[j], u.v[j]);
   reinterpret_cast<bf16x8*>(out)[i] = o;
 }
 
@@ -40,7 +39,7 @@ __global__ __launch_bounds__(BLOCK) void swiglu_fused_kernel(
   bf16x8 o;
 #pragma unroll
   for (int j = 0; j < 8; ++j)
-    o.v[j] = f2bf(silu(bf2f(g.v[j])) * bf2f(u.v[j]));
+    o.v[j] = swiglu_bf16(g.v[j], u.v[j]);
   *reinterpret_cast<bf16x8*>(out + r * I + c) = o;
 }
 
