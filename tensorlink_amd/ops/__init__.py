@@ -445,6 +445,7 @@ _LIB_CLASSES = frozenset(
 
 
 def _gemm_class(N: int, K: int) -> str:
+    # "wide" is TL_GEMM_WIDE_N in ops/csrc/gemm_policy.hpp: keep them equal
     if N >= 65536:
         return "wide"
     if N >= 16384:
@@ -536,9 +537,7 @@ def linear_partials(x: torch.Tensor, weight: torch.Tensor,
     devices/dtypes, M above GEMM_M_MAX, library-routed classes, n_split
     == 1) returns :func:`linear`'s tensor."""
     global gemm_dispatch_count
-    if (x.is_cuda and not torch.is_grad_enabled()
-            and x.dtype == torch.bfloat16
-            and not _os.environ.get("TL_NO_SKINNY")):
+    if _family_input(x):
         K = x.shape[-1]
         M = x.numel() // K
         N = weight.shape[0]

@@ -7,6 +7,8 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
+#include "gemm_policy.hpp"
+
 extern "C" {
 void tl_rmsnorm_fwd(const void* x, const void* residual, const void* w,
                     void* y, void* r_out, void* rstd, int64_t N, int H,
@@ -51,16 +53,10 @@ void tl_decode_attn_mfma(const void* q, const void* k_cache,
                          hipStream_t stream);
 void tl_skinny_gemm(const void* x, const void* w, const void* bias,
                     void* out, void* partial, int M, int N, int K,
-                    int n_split, hipStream_t stream);
+                    int n_split, int reduce, hipStream_t stream);
 void tl_gemm_tiled(const void* x, const void* w, const void* bias, void* out,
                    void* partial, int M, int N, int K, int n_split,
-                   hipStream_t stream);
-void tl_skinny_gemm_partials(const void* x, const void* w, const void* bias,
-                             void* out, void* partial, int M, int N, int K,
-                             int n_split, hipStream_t stream);
-void tl_gemm_tiled_partials(const void* x, const void* w, const void* bias,
-                            void* out, void* partial, int M, int N, int K,
-                            int n_split, hipStream_t stream);
+                   int reduce, hipStream_t stream);
 void tl_gemm_colbal(const void* x, const void* w, void* out, int M, int N,
                     int K, int n_blocks, int fused, hipStream_t stream);
 void tl_sample(const void* logits, const void* temps, const void* top_ps,
@@ -94,14 +90,6 @@ namespace {
 
 hipStream_t cur_stream() {
   return c10::hip::getCurrentHIPStream().stream();
-}
-
-// host copy of tl_split_for_len (common.hpp — keep in sync; this file is
-// compiled by plain g++ so it cannot include the device header)
-int tl_split_for_len(int L) {
-  int ns = 1;
-  while (ns < 16 && L > 1024 * ns) ns <<= 1;
-  return ns;
 }
 
 #define CHECK_IN(t, d)                                              \
@@ -287,7 +275,7 @@ Tensor decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor seq_lens,
   int per_row = 0;
   if (n_split <= 0) {
     // auto: per-ROW split from each row's own length (tl_split_for_len,
-    // common.hpp) so a sequence's numerics are batch-independent; the
+    // gemm_policy.hpp) so a sequence's numerics are batch-independent; the
     // launch z-width comes from a batch-shape-free host bound on L
     // (cache capacity, which bounds seq_lens + len_add too), no device
     // sync needed.
@@ -446,100 +434,65 @@ Tensor swiglu_fused(Tensor gu) {
   return out;
 }
 
-// Split-K policy SHARED by the streaming (M<=64) and tiled (M>64) GEMM
-// kernels. It depends only on (N, K) — never M — so a row's accumulation
-// (split boundaries + s-ordered reduce) is bitwise identical at every M:
-// the serving engine's exact-greedy guarantee rests on this.
-// split-block target (~blocks before M/z tiling); env-tunable for
-// in-pipeline A/B — read ONCE so the policy stays (N,K)-pure in-process
-static int gemm_split_target() {
-  static int t = [] {
+// Split-K policy SHARED by the streaming and tiled GEMM kernels
+// (gemm_n_split_for, gemm_policy.hpp): pure in (N, K), never M. The
+// split-block target is env-tunable for in-pipeline A/B — read ONCE so the
+// policy stays (N,K)-pure in-process.
+static int gemm_n_split(int N, int K) {
+  static const int target = [] {
     const char* e = getenv("TL_GEMM_SPLIT_TARGET");
     return e ? atoi(e) : 256;
   }();
-  return t;
+  return gemm_n_split_for(N, K, target);
 }
 
-static int gemm_n_split(int N, int K) {
-  if (N >= 65536) {
-    // 256x256-tile class (gemm_tiled_sq, lm_head widths): enough
-    // column panels to fill the chip without splitting
-    int n_split = 1;
-    while (((N + 255) / 256) * n_split < gemm_split_target() &&
-           n_split < 16 && (K / 64) / (n_split * 2) >= 16)
-      n_split <<= 1;
-    return n_split;
+// x @ W^T (+ bias) through the streaming (M <= TL_GEMM_STREAM_M) or tiled
+// kernel. reduce: the bf16 output [.., N]. !reduce: the fp32 split-K
+// partials [n_split, .., N] for a consumer kernel to sum (s order from 0,
+// then bias, then one bf16 rounding — exactly what the reduce kernel does),
+// so bias is NOT applied; when the policy gives n_split == 1 there is
+// nothing to hand out and the bf16 output comes back, bias included.
+static Tensor family_gemm(Tensor x, Tensor w, c10::optional<Tensor> bias,
+                          bool reduce) {
+  CHECK_IN(x, torch::kBFloat16);
+  CHECK_IN(w, torch::kBFloat16);
+  const int K = x.size(-1);
+  const int64_t M = x.numel() / K;
+  const int N = w.size(0);
+  TORCH_CHECK(w.size(1) == K, "K mismatch");
+  TORCH_CHECK(K % 32 == 0 && N % 64 == 0, "unsupported shape");
+  const int n_split = gemm_n_split(N, K);
+  const bool hand_out = !reduce && n_split > 1;
+  auto sizes = x.sizes().vec();
+  sizes.back() = N;
+  Tensor out, partial;
+  const void* bp = nullptr;
+  if (hand_out) {
+    sizes.insert(sizes.begin(), n_split);
+    partial = torch::empty(sizes, x.options().dtype(torch::kFloat));
+  } else {
+    out = torch::empty(sizes, x.options());
+    if (bias.has_value()) {
+      CHECK_IN(bias.value(), torch::kBFloat16);
+      bp = bias->data_ptr();
+    }
+    if (n_split > 1)
+      partial = torch::empty({(int64_t)n_split * M * N},
+                             x.options().dtype(torch::kFloat));
   }
-  // split K so (N/64)*n_split lands near the target block count
-  int n_split = 1;
-  while ((N / 64) * n_split < gemm_split_target() && n_split < 8 &&
-         (K / 32) / (n_split * 2) >= 2)
-    n_split <<= 1;
-  return n_split;
+  auto launch = M <= TL_GEMM_STREAM_M ? tl_skinny_gemm : tl_gemm_tiled;
+  launch(x.data_ptr(), w.data_ptr(), bp, hand_out ? nullptr : out.data_ptr(),
+         n_split > 1 ? partial.data_ptr() : nullptr, (int)M, N, K, n_split,
+         hand_out ? 0 : 1, cur_stream());
+  return hand_out ? partial : out;
 }
 
 Tensor skinny_gemm(Tensor x, Tensor w, c10::optional<Tensor> bias) {
-  CHECK_IN(x, torch::kBFloat16);
-  CHECK_IN(w, torch::kBFloat16);
-  const int K = x.size(-1);
-  const int64_t M = x.numel() / K;
-  const int N = w.size(0);
-  TORCH_CHECK(w.size(1) == K, "K mismatch");
-  TORCH_CHECK(K % 32 == 0 && N % 64 == 0, "unsupported shape");
-  auto sizes = x.sizes().vec();
-  sizes.back() = N;
-  auto out = torch::empty(sizes, x.options());
-  const void* bp = nullptr;
-  if (bias.has_value()) {
-    CHECK_IN(bias.value(), torch::kBFloat16);
-    bp = bias->data_ptr();
-  }
-  const int n_split = gemm_n_split(N, K);
-  Tensor partial;
-  void* pp = nullptr;
-  if (n_split > 1) {
-    partial = torch::empty({(int64_t)n_split * M * N},
-                           x.options().dtype(torch::kFloat));
-    pp = partial.data_ptr();
-  }
-  if (M <= 64)
-    tl_skinny_gemm(x.data_ptr(), w.data_ptr(), bp, out.data_ptr(), pp,
-                   (int)M, N, K, n_split, cur_stream());
-  else
-    tl_gemm_tiled(x.data_ptr(), w.data_ptr(), bp, out.data_ptr(), pp,
-                  (int)M, N, K, n_split, cur_stream());
-  return out;
+  return family_gemm(x, w, bias, true);
 }
 
-// skinny_gemm without the reduce pass: returns the fp32 split-K partials
-// [n_split, .., N] for a consumer kernel to sum (s order from 0, then
-// bias, then one bf16 rounding — exactly what the reduce kernels do), so
-// bias is NOT applied. When the policy gives n_split == 1 there is nothing
-// to hand out and the bf16 output comes back as from skinny_gemm, bias
-// included.
 Tensor skinny_gemm_partials(Tensor x, Tensor w, c10::optional<Tensor> bias) {
-  CHECK_IN(x, torch::kBFloat16);
-  CHECK_IN(w, torch::kBFloat16);
-  const int K = x.size(-1);
-  const int64_t M = x.numel() / K;
-  const int N = w.size(0);
-  TORCH_CHECK(w.size(1) == K, "K mismatch");
-  TORCH_CHECK(K % 32 == 0 && N % 64 == 0, "unsupported shape");
-  const int n_split = gemm_n_split(N, K);
-  if (n_split == 1) return skinny_gemm(x, w, bias);
-  auto sizes = x.sizes().vec();
-  sizes.back() = N;
-  sizes.insert(sizes.begin(), n_split);
-  auto partial = torch::empty(sizes, x.options().dtype(torch::kFloat));
-  if (M <= 64)
-    tl_skinny_gemm_partials(x.data_ptr(), w.data_ptr(), nullptr, nullptr,
-                            partial.data_ptr(), (int)M, N, K, n_split,
-                            cur_stream());
-  else
-    tl_gemm_tiled_partials(x.data_ptr(), w.data_ptr(), nullptr, nullptr,
-                           partial.data_ptr(), (int)M, N, K, n_split,
-                           cur_stream());
-  return partial;
+  return family_gemm(x, w, bias, false);
 }
 
 // CU count of a device, read once: the column-balanced GEMM launches one
@@ -596,19 +549,8 @@ Tensor gemm_colbal_swiglu(Tensor x, Tensor w_gate_up, int64_t n_blocks) {
   return gemm_colbal_impl(x, w_gate_up, n_blocks, true);
 }
 
-// Split-K policy of the MXFP4 weight GEMM (mxfp4_gemm.hip). (N,K)-pure like
-// gemm_n_split, but counted in the kernel's 128-k steps: a column's packed
-// bytes are 4x fewer than bf16, so a split must keep >= 2 steps.
-// One loop serves both MXFP4 kernels: `blocks` is the grid before the
-// split, N/64 for the dense kernel and (N/64)*E for the grouped one.
-static int mxfp4_split_for_blocks(int blocks, int K) {
-  int n_split = 1;
-  while (blocks * n_split < 256 && n_split < 8 &&
-         (K / 128) / (n_split * 2) >= 2)
-    n_split <<= 1;
-  return n_split;
-}
-
+// Split-K policy of the MXFP4 kernels: mxfp4_split_for_blocks
+// (gemm_policy.hpp) over the grid before the split.
 static int mxfp4_n_split(int N, int K) {
   return mxfp4_split_for_blocks(N / 64, K);
 }

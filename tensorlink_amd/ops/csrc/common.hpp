@@ -8,6 +8,8 @@
 #include <hip/hip_fp16.h>
 #include <cstdint>
 
+#include "gemm_policy.hpp"
+
 #define WAVE_SIZE 64
 
 #define DEVINLINE __device__ __forceinline__
@@ -24,6 +26,12 @@ union f32x4_u {
   float4 f4;
   float f[4];
 };
+
+// MFMA operand / accumulator vectors (mfma_f32_16x16x32_bf16: 8 bf16 per
+// lane in, 4 f32 per lane out) — also what ds_read_b128 and the LDS
+// transpose read below deliver.
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
 DEVINLINE float bf2f(bf16 x) { return __bfloat162float(x); }
 DEVINLINE bf16 f2bf(float x) { return __float2bfloat16(x); }
@@ -70,16 +78,7 @@ DEVINLINE float block_reduce_sum(float x, float* lds) {
 
 __host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-// Flash-decode split count for ONE row of length L. Depends only on L —
-// never on batch size or launch shape — so a sequence's attention
-// numerics are identical whatever batch it is decoded in (the serving
-// engine's exact-greedy guarantee; see decode_attn_mfma.hip). Monotone
-// in L, so a host-side length upper bound gives a valid launch width.
-__host__ __device__ inline int tl_split_for_len(int L) {
-  int ns = 1;
-  while (ns < 16 && L > 1024 * ns) ns <<= 1;
-  return ns;
-}
+// tl_split_for_len (flash-decode split count per row): gemm_policy.hpp.
 __host__ __device__ inline int64_t cdiv64(int64_t a, int64_t b) {
   return (a + b - 1) / b;
 }
@@ -145,9 +144,7 @@ DEVINLINE void sum_partials8(const float* (&p)[NV],
 // fragment elements in order. The waitcnt lives INSIDE the asm so the
 // consuming MFMA (ordered by its register dependency) is safe.
 // ---------------------------------------------------------------------------
-typedef __bf16 tr_bf16x8 __attribute__((ext_vector_type(8)));
-
-DEVINLINE tr_bf16x8 ds_read_tr16_frag(unsigned addr_bytes) {
+DEVINLINE bf16x8_t ds_read_tr16_frag(unsigned addr_bytes) {
   unsigned long long lo, hi;
   asm volatile(
       "ds_read_b64_tr_b16 %0, %2\n\t"
@@ -157,7 +154,7 @@ DEVINLINE tr_bf16x8 ds_read_tr16_frag(unsigned addr_bytes) {
       : "v"(addr_bytes));
   union {
     struct { unsigned long long a, b; } u;
-    tr_bf16x8 v;
+    bf16x8_t v;
   } cvt;
   cvt.u.a = lo;
   cvt.u.b = hi;

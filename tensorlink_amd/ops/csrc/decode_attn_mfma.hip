@@ -26,9 +26,6 @@ constexpr int BLOCK = 256;
 constexpr int NWAVE = 4;
 constexpr int KT = 16;            // keys per MFMA tile
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
 // out layout when SPLIT > 1: partial [B, Hq, SPLIT, D] float, ml [B, Hq,
 // SPLIT, 2] float (m, l). SPLIT == 1 writes bf16 out directly.
 // PAGED: k_cache/v_cache are page pools [n_pages, Hkv, PAGE, D] and

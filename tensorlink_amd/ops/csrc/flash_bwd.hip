@@ -30,9 +30,6 @@ constexpr int BLOCK = 256;   // 4 waves
 constexpr int BT = 64;       // tile size (keys and q rows)
 constexpr int PPAD = 8;
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
 constexpr int PSTRIDE = 32 * 16 + 8;
 
 // stage a [BT][D] tile as both padded rows and tr16 panels

@@ -20,8 +20,8 @@
 // (BN <= 160). No K split, no partials, nothing shared between workgroups.
 //
 // Pipeline: both operands go through LDS by global_load_lds width 16 in
-// full 128-byte lines, XOR swizzle on the source address, fragments by
-// ds_read_b128 (the image gemm_tiled.hip uses). A stage is (256 + 160)
+// full 128-byte lines, in the family's swizzled image (gemm_family.hpp),
+// fragments by ds_read_b128. A stage is (256 + 160)
 // rows x 64 k = 52 KB; three stages form a ring with ONE barrier per
 // chunk: each wave waits (counted vmcnt, never 0 before the last chunk) for
 // its own loads of chunk t+1, the barrier makes chunk t+1 visible and
@@ -37,13 +37,10 @@
 // slots 5..9, so the epilogue finds gate and up of one output element in
 // the same image row and applies swiglu_bf16 (swiglu_common.hpp) to them.
 
-#include "common.hpp"
+#include "gemm_family.hpp"
 #include "swiglu_common.hpp"
 
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
 constexpr int CB_BM = 256;               // rows per workgroup
 constexpr int CB_SLOTS = 10;             // 16-column MFMA tiles per stage
@@ -53,11 +50,6 @@ constexpr int CB_STAGE_ELEMS = CB_ROWS * 64;
 // epilogue image row stride: 160 columns + 8 pad, so the four row groups a
 // wave writes at once (rows 4 apart) fall on different banks
 constexpr int CB_CPAD = 168;
-
-template <int N>
-DEVINLINE void cb_waitcnt_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 template <int FUSED>
 __global__ __launch_bounds__(512, 1) void gemm_colbal_kernel(
@@ -72,7 +64,7 @@ __global__ __launch_bounds__(512, 1) void gemm_colbal_kernel(
   const int quad = lane >> 4;
   const int wm = wave >> 1;                // 0..3: 64-row band
   const int wn = wave & 1;                 // 0..1: 5-slot band
-  const int l8 = lane >> 3, c8 = lane & 7;
+  const int l8 = lane >> 3;
   const int m_base = blockIdx.z * CB_BM;
 
   // slots per column tile, tiles per sub-range
@@ -123,23 +115,14 @@ __global__ __launch_bounds__(512, 1) void gemm_colbal_kernel(
     // chunks over 8 waves); the count is wave-uniform
     auto stage = [&](int bufi, int k0) {
       bf16* sbase = lds + bufi * CB_STAGE_ELEMS;
-      const int kc = min(k0 + (c8 ^ l8) * 8, K - 8);
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        auto gsrc = (const __attribute__((address_space(1))) void*)(
-            x + xoff[g] + kc);
-        auto ldst = (__attribute__((address_space(3))) void*)(
-            sbase + (wave * 4 + g) * 8 * 64);
-        __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 0, 0);
-      }
+      for (int g = 0; g < 4; ++g)
+        stage_8x64(x + xoff[g], lane, k0, K, sbase + (wave * 4 + g) * 8 * 64);
 #pragma unroll
       for (int g = 0; g < 3; ++g) {
         if (g == 2 && wave >= 4) break;
-        auto gsrc = (const __attribute__((address_space(1))) void*)(
-            w + woff[g] + kc);
-        auto ldst = (__attribute__((address_space(3))) void*)(
-            sbase + (CB_BM + (wave + g * 8) * 8) * 64);
-        __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 0, 0);
+        stage_8x64(w + woff[g], lane, k0, K,
+                   sbase + (CB_BM + (wave + g * 8) * 8) * 64);
       }
     };
 
@@ -151,19 +134,13 @@ __global__ __launch_bounds__(512, 1) void gemm_colbal_kernel(
     bf16x8_t bfrag[2][5], afrag[2][4];
     auto read_frags = [&](int kk) {
 #pragma unroll
-      for (int nt = 0; nt < 5; ++nt) {
-        const int wrow = (wn * 5 + nt) * 16 + col;
-        const int wslot = (kk * 4 + quad) ^ (wrow & 7);
-        bfrag[kk][nt] = *reinterpret_cast<const bf16x8_t*>(
-            sb + (CB_BM + wrow) * 64 + wslot * 8);
-      }
+      for (int nt = 0; nt < 5; ++nt)
+        bfrag[kk][nt] = lds_frag(sb + CB_BM * 64, (wn * 5 + nt) * 16 + col,
+                                 kk * 4 + quad);
 #pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        const int row = wm * 64 + mt * 16 + col;
-        const int slot = (kk * 4 + quad) ^ (row & 7);
-        afrag[kk][mt] = *reinterpret_cast<const bf16x8_t*>(
-            sb + row * 64 + slot * 8);
-      }
+      for (int mt = 0; mt < 4; ++mt)
+        afrag[kk][mt] =
+            lds_frag(sb, wm * 64 + mt * 16 + col, kk * 4 + quad);
     };
     auto mfmas = [&](int kk) {
 #pragma unroll
@@ -177,10 +154,10 @@ __global__ __launch_bounds__(512, 1) void gemm_colbal_kernel(
     auto retire = [&](int t) {
       // own loads of chunk t landed; chunk t+1 stays in flight
       if (t + 1 < n_chunks) {
-        if (wave < 4) cb_waitcnt_vm<7>();
-        else cb_waitcnt_vm<6>();
+        if (wave < 4) waitcnt_vm<7>();
+        else waitcnt_vm<6>();
       } else {
-        cb_waitcnt_vm<0>();
+        waitcnt_vm<0>();
       }
       // this wave's reads of chunk t-1 are done before it passes the
       // barrier that lets others overwrite that stage

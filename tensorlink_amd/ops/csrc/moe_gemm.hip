@@ -15,16 +15,17 @@
 // grid (N/64, E); block = 4 waves; per 64-row m-chunk the x slab stages
 // through LDS by global_load_lds (indirect rows via tok_idx) and W
 // streams from HBM; K accumulates in 64-chunks, two
-// mfma_f32_16x16x32_bf16 per chunk in kk order (family contract).
+// mfma_f32_16x16x32_bf16 per chunk in kk order (family contract,
+// gemm_family.hpp). The staging piece and the fragment read below are the
+// family's stage_8x64 / lds_frag written out: with the helpers this kernel's
+// occupancy and its speed moved (profiles/gemm_family_refactor.md), so it
+// keeps its own body; keep the swizzle equal to gemm_family.hpp's rule.
 
-#include "common.hpp"
+#include "gemm_family.hpp"
 
 namespace {
 
 constexpr int BLOCK = 256;
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
 // fp8 e4m3 (OCP) -> f32 for the LUT (host-independent, computed on
 // device at kernel start: 256 entries)
@@ -99,11 +100,7 @@ __global__ __launch_bounds__(BLOCK, 2) void moe_gemm_kernel(
         const int p = m0 + mb + min(row, mrows - 1);                        \
         const int xr = tok_idx ? tok_idx[p] : p;                            \
         const int kc = min((k0) + (c8 ^ (row & 7)) * 8, K - 8);             \
-        auto gsrc = (const __attribute__((address_space(1))) void*)(        \
-            x + (int64_t)xr * K + kc);                                      \
-        auto ldst = (__attribute__((address_space(3))) void*)(              \
-            &lds[bufi][chunk * 8][0]);                                      \
-        __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 0, 0);             \
+        glds16(x + (int64_t)xr * K + kc, &lds[bufi][chunk * 8][0]);         \
       }                                                                     \
     }
 

@@ -1,11 +1,16 @@
 // Shared pieces of the MXFP4 weight-only kernels (mxfp4_gemm.hip: one
-// weight; mxfp4_moe_gemm.hip: grouped experts). One copy of the e2m1
-// decode, the byte -> float2 table build, the split-K slice formula and the
-// s-ordered reduce, so the two kernels cannot drift apart: wherever their
-// split counts agree a row is bitwise the same from either.
+// weight; mxfp4_moe_gemm.hip: grouped experts), on top of the family
+// header, which brings the s-ordered reduce: the e2m1 decode, the byte ->
+// float2 table build and the 128-k split slice, so the two kernels cannot
+// drift apart there: wherever their split counts agree a row is bitwise
+// the same from either. The 128-k step body, the three slice lines and the
+// epilogue are still written out in both kernels: as a shared k loop, and
+// again with only family_k_slice<SPLIT, 128> and store_cfrag_* in their
+// place, the MT = 4 kernels measured 3-5 % slower on the gate_up and
+// Mixtral down shapes (profiles/gemm_family_refactor.md).
 #pragma once
 
-#include "common.hpp"
+#include "gemm_family.hpp"
 
 namespace {
 
@@ -35,27 +40,14 @@ DEVINLINE void mxfp4_build_lut(unsigned char* lut) {
   *reinterpret_cast<mx_f32x2*>(lut + b * 8) = v;
 }
 
-// k range of one split: whole 128-k steps, ceil-divided over the splits.
-// Split s covers [s * k_per, min(K, (s + 1) * k_per)); a trailing split
-// may be empty and then contributes zeros.
+// k range of one split: whole 128-k steps, ceil-divided over the splits
+// (family_k_slice's rule at STEP = 128; see the top of this file for why
+// it is not that call). Split s covers [s * k_per,
+// min(K, (s + 1) * k_per)); a trailing split may be empty and then
+// contributes zeros.
 DEVINLINE int mxfp4_k_per(int K, int n_split) {
   const int steps = K / MX_KSTEP;
   return ((steps + n_split - 1) / n_split) * MX_KSTEP;
-}
-
-// out[i] = bf16(sum_s partial[s][i] (+ bias)), s ascending: no atomics, so
-// the sum order is fixed.
-template <int HAS_BIAS>
-__global__ void mxfp4_reduce_kernel(const float* __restrict__ partial,
-                                    const bf16* __restrict__ bias,
-                                    bf16* __restrict__ out, int64_t MN,
-                                    int N, int n_split) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= MN) return;
-  float acc = 0.f;
-  for (int s = 0; s < n_split; ++s) acc += partial[s * MN + i];
-  if (HAS_BIAS) acc += bf2f(bias[i % N]);
-  out[i] = f2bf(acc);
 }
 
 }  // namespace

@@ -34,16 +34,14 @@
 
 namespace {
 
-// decode, table build, split slice and reduce: mxfp4_common.hpp, shared
-// with the grouped expert kernel (mxfp4_moe_gemm.hip)
+// decode, table build and split slice: mxfp4_common.hpp, shared with the
+// grouped expert kernel (mxfp4_moe_gemm.hip)
 constexpr int BLOCK = MX_BLOCK;
 constexpr int KSTEP = MX_KSTEP;            // k per main-loop step
 constexpr int ROW_BYTES = MX_ROW_BYTES;    // one slab row (bf16)
 constexpr int LUT_BYTES = MX_LUT_BYTES;    // byte -> float2
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f32x2 = mx_f32x2;
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
 template <int MT, int HAS_BIAS, int SPLIT>
 __global__ __launch_bounds__(BLOCK, 2) void mxfp4_gemm_kernel(
@@ -95,11 +93,8 @@ __global__ __launch_bounds__(BLOCK, 2) void mxfp4_gemm_kernel(
       const int row = chunk * 4 + l16;                                      \
       const int xr = mb + min(row, mrows - 1);                              \
       const int kc = (k0) + (p16 ^ (row & 15)) * 8;                         \
-      auto gsrc = (const __attribute__((address_space(1))) void*)(          \
-          x + (int64_t)xr * K + kc);                                        \
-      auto ldst = (__attribute__((address_space(3))) void*)(                \
-          smem + (bufi) * SLAB_BYTES + chunk * 4 * ROW_BYTES);              \
-      __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 0, 0);               \
+      glds16(x + (int64_t)xr * K + kc,                                      \
+             smem + (bufi) * SLAB_BYTES + chunk * 4 * ROW_BYTES);           \
     }
 
     if (k_begin < k_end) MX_GLDS_TILE(0, k_begin);
@@ -172,6 +167,16 @@ __global__ __launch_bounds__(BLOCK, 2) void mxfp4_gemm_kernel(
   }
 }
 
+template <int MT>
+void mxfp4_launch_mt(const void* x, const void* packed, const void* exps,
+                     const void* bias, void* out, void* partial, int M,
+                     int N, int K, int n_split, hipStream_t stream) {
+  launch_variant(mxfp4_gemm_kernel<MT, 0, 1>, mxfp4_gemm_kernel<MT, 1, 0>,
+                 mxfp4_gemm_kernel<MT, 0, 0>, n_split, bias,
+                 dim3(N / 64, n_split), dim3(BLOCK), stream, x, packed,
+                 exps, bias, out, partial, M, N, K, n_split);
+}
+
 }  // namespace
 
 extern "C" {
@@ -181,43 +186,17 @@ extern "C" {
 void tl_mxfp4_gemm(const void* x, const void* packed, const void* exps,
                    const void* bias, void* out, void* partial, int M, int N,
                    int K, int n_split, hipStream_t stream) {
-  const int split = n_split > 1 ? 1 : 0;
-  dim3 grid(N / 64, n_split), block(BLOCK);
-#define DISPATCH(MT)                                                        \
-  do {                                                                      \
-    if (split) {                                                            \
-      hipLaunchKernelGGL((mxfp4_gemm_kernel<MT, 0, 1>), grid, block, 0,     \
-                         stream, (const bf16*)x, (const uint8_t*)packed,    \
-                         (const int8_t*)exps, nullptr, (bf16*)out,          \
-                         (float*)partial, M, N, K, n_split);                \
-    } else if (bias) {                                                      \
-      hipLaunchKernelGGL((mxfp4_gemm_kernel<MT, 1, 0>), grid, block, 0,     \
-                         stream, (const bf16*)x, (const uint8_t*)packed,    \
-                         (const int8_t*)exps, (const bf16*)bias,            \
-                         (bf16*)out, nullptr, M, N, K, 1);                  \
-    } else {                                                                \
-      hipLaunchKernelGGL((mxfp4_gemm_kernel<MT, 0, 0>), grid, block, 0,     \
-                         stream, (const bf16*)x, (const uint8_t*)packed,    \
-                         (const int8_t*)exps, nullptr, (bf16*)out, nullptr, \
-                         M, N, K, 1);                                       \
-    }                                                                       \
-  } while (0)
-  if (M <= 16) DISPATCH(1);
-  else if (M <= 32) DISPATCH(2);
-  else DISPATCH(4);
-#undef DISPATCH
-  if (split) {
-    const int64_t MN = (int64_t)M * N;
-    dim3 rgrid((uint32_t)((MN + 255) / 256)), rblock(256);
-    if (bias)
-      hipLaunchKernelGGL((mxfp4_reduce_kernel<1>), rgrid, rblock, 0, stream,
-                         (const float*)partial, (const bf16*)bias,
-                         (bf16*)out, MN, N, n_split);
-    else
-      hipLaunchKernelGGL((mxfp4_reduce_kernel<0>), rgrid, rblock, 0, stream,
-                         (const float*)partial, nullptr, (bf16*)out, MN, N,
-                         n_split);
-  }
+  if (M <= 16)
+    mxfp4_launch_mt<1>(x, packed, exps, bias, out, partial, M, N, K, n_split,
+                       stream);
+  else if (M <= 32)
+    mxfp4_launch_mt<2>(x, packed, exps, bias, out, partial, M, N, K, n_split,
+                       stream);
+  else
+    mxfp4_launch_mt<4>(x, packed, exps, bias, out, partial, M, N, K, n_split,
+                       stream);
+  if (n_split > 1)
+    launch_splitk_reduce(partial, bias, out, M, N, n_split, stream);
 }
 
 }  // extern "C"

@@ -38,9 +38,7 @@ constexpr int KSTEP = MX_KSTEP;
 constexpr int ROW_BYTES = MX_ROW_BYTES;
 constexpr int LUT_BYTES = MX_LUT_BYTES;
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f32x2 = mx_f32x2;
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
 template <int MT, int SPLIT>
 __global__ __launch_bounds__(BLOCK, 2) void mxfp4_moe_gemm_kernel(
@@ -112,11 +110,8 @@ __global__ __launch_bounds__(BLOCK, 2) void mxfp4_moe_gemm_kernel(
 #define MXM_GLDS_TILE(bufi, k0)                                             \
     _Pragma("unroll") for (int g = 0; g < MT; ++g) {                        \
       const int chunk = wave * MT + g;                                      \
-      auto gsrc = (const __attribute__((address_space(1))) void*)(          \
-          xsrc[g] + (k0));                                                  \
-      auto ldst = (__attribute__((address_space(3))) void*)(                \
-          smem + (bufi) * SLAB_BYTES + chunk * 4 * ROW_BYTES);              \
-      __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 0, 0);               \
+      glds16(xsrc[g] + (k0),                                                \
+             smem + (bufi) * SLAB_BYTES + chunk * 4 * ROW_BYTES);           \
     }
 
     if (k_begin < k_end) MXM_GLDS_TILE(0, k_begin);
@@ -188,6 +183,19 @@ __global__ __launch_bounds__(BLOCK, 2) void mxfp4_moe_gemm_kernel(
   }
 }
 
+template <int MT>
+void mxfp4_moe_launch_mt(const void* x, const void* tok_idx,
+                         const void* seg_off, const void* p_ptrs,
+                         const void* e_ptrs, void* out, void* partial, int T,
+                         int P, int E, int N, int K, int n_split,
+                         hipStream_t stream) {
+  // no bias: the plain kernel stands in for the bias variant
+  launch_variant(mxfp4_moe_gemm_kernel<MT, 1>, mxfp4_moe_gemm_kernel<MT, 0>,
+                 mxfp4_moe_gemm_kernel<MT, 0>, n_split, nullptr,
+                 dim3(N / 64, E, n_split), dim3(BLOCK), stream, x, tok_idx,
+                 seg_off, p_ptrs, e_ptrs, out, partial, T, P, N, K, n_split);
+}
+
 }  // namespace
 
 extern "C" {
@@ -200,34 +208,17 @@ void tl_mxfp4_moe_gemm(const void* x, const void* tok_idx,
                        const void* e_ptrs, void* out, void* partial, int T,
                        int P, int E, int N, int K, int n_split,
                        hipStream_t stream) {
-  const int split = n_split > 1 ? 1 : 0;
-  dim3 grid(N / 64, E, n_split), block(BLOCK);
-#define DISPATCH(MT)                                                        \
-  do {                                                                      \
-    if (split)                                                              \
-      hipLaunchKernelGGL((mxfp4_moe_gemm_kernel<MT, 1>), grid, block, 0,    \
-                         stream, (const bf16*)x, (const int*)tok_idx,       \
-                         (const int*)seg_off, (const uint64_t*)p_ptrs,      \
-                         (const uint64_t*)e_ptrs, (bf16*)out,               \
-                         (float*)partial, T, P, N, K, n_split);             \
-    else                                                                    \
-      hipLaunchKernelGGL((mxfp4_moe_gemm_kernel<MT, 0>), grid, block, 0,    \
-                         stream, (const bf16*)x, (const int*)tok_idx,       \
-                         (const int*)seg_off, (const uint64_t*)p_ptrs,      \
-                         (const uint64_t*)e_ptrs, (bf16*)out, nullptr, T,   \
-                         P, N, K, 1);                                       \
-  } while (0)
-  if (P <= 16) DISPATCH(1);
-  else if (P <= 32) DISPATCH(2);
-  else DISPATCH(4);
-#undef DISPATCH
-  if (split) {
-    const int64_t MN = (int64_t)P * N;
-    dim3 rgrid((uint32_t)((MN + 255) / 256)), rblock(256);
-    hipLaunchKernelGGL((mxfp4_reduce_kernel<0>), rgrid, rblock, 0, stream,
-                       (const float*)partial, nullptr, (bf16*)out, MN, N,
-                       n_split);
-  }
+  if (P <= 16)
+    mxfp4_moe_launch_mt<1>(x, tok_idx, seg_off, p_ptrs, e_ptrs, out, partial,
+                           T, P, E, N, K, n_split, stream);
+  else if (P <= 32)
+    mxfp4_moe_launch_mt<2>(x, tok_idx, seg_off, p_ptrs, e_ptrs, out, partial,
+                           T, P, E, N, K, n_split, stream);
+  else
+    mxfp4_moe_launch_mt<4>(x, tok_idx, seg_off, p_ptrs, e_ptrs, out, partial,
+                           T, P, E, N, K, n_split, stream);
+  if (n_split > 1)
+    launch_splitk_reduce(partial, nullptr, out, P, N, n_split, stream);
 }
 
 }  // extern "C"

@@ -26,9 +26,6 @@ constexpr int BM = 64;       // query rows per block
 constexpr int BN = 64;       // key cols per tile
 constexpr int PPAD = 8;      // P row pad: stride 72 elems = 144 B
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
 // Sq = query length, Skv = key/value length, q_off = global position of
 // query row 0 (chunked prefill: Skv = q_off + Sq history+chunk keys; the
 // plain full prefill is Sq == Skv, q_off == 0).

@@ -2,7 +2,8 @@
 //
 // torch Linear stores W as [N, K] row-major, so both operands are
 // k-contiguous — the same A·B^T fragment pattern as QK^T. At decode M
-// (<= 256 rows) the GEMM is pure W-streaming.
+// (<= 64 rows, TL_GEMM_STREAM_M; gemm_tiled.hip serves the rest) the GEMM
+// is pure W-streaming.
 //
 // v3 geometry (measured on MI355X):
 //   v1 gridded over M: every W panel re-streamed per M-tile -> 0.4 TB/s.
@@ -15,15 +16,18 @@
 //   from HBM exactly once chip-wide.
 // Grid (N/64, SPLITK); block = 4 waves; wave w owns columns w*16; SPLITK
 // slices K when N/64 can't fill the chip (fp32 partials + reduce kernel).
+//
+// The slice, the staging piece, the fragment read and the epilogue below are
+// the family's family_k_slice / stage_8x64 / lds_frag / store_cfrag_*
+// (gemm_family.hpp) written out: with the helpers this kernel read 1 %
+// slower at M = 64 on deep K (profiles/gemm_family_refactor.md), so it
+// keeps its own body. Keep the swizzle and the slice equal to the header's.
 
-#include "common.hpp"
+#include "gemm_family.hpp"
 
 namespace {
 
 constexpr int BLOCK = 256;
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
 template <int MT, int HAS_BIAS, int SPLIT>
 __global__ __launch_bounds__(BLOCK, 2) void skinny_gemm_kernel(
@@ -72,11 +76,7 @@ __global__ __launch_bounds__(BLOCK, 2) void skinny_gemm_kernel(
       const int row = chunk * 8 + l8;                                       \
       const int xr = min(row, M - 1);                                       \
       const int kc = min((k0) + (c8 ^ (row & 7)) * 8, K - 8);               \
-      auto gsrc = (const __attribute__((address_space(1))) void*)(          \
-          x + (int64_t)xr * K + kc);                                        \
-      auto ldst = (__attribute__((address_space(3))) void*)(                \
-          &x_lds[bufi][chunk * 8][0]);                                      \
-      __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 0, 0);               \
+      glds16(x + (int64_t)xr * K + kc, &x_lds[bufi][chunk * 8][0]);         \
     }                                                                       \
   }
 
@@ -127,82 +127,41 @@ __global__ __launch_bounds__(BLOCK, 2) void skinny_gemm_kernel(
   }
 }
 
-template <int HAS_BIAS>
-__global__ void skinny_reduce_kernel(const float* __restrict__ partial,
-                                     const bf16* __restrict__ bias,
-                                     bf16* __restrict__ out, int64_t MN,
-                                     int N, int n_split) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= MN) return;
-  float acc = 0.f;
-  for (int s = 0; s < n_split; ++s) acc += partial[s * MN + i];
-  if (HAS_BIAS) acc += bf2f(bias[i % N]);
-  out[i] = f2bf(acc);
-}
-
-// reduce == 0 leaves the fp32 partials for the consumer to sum (in s
-// order, then bias) — rope_append / rmsnorm read them directly.
-void skinny_launch(const void* x, const void* w, const void* bias,
-                   void* out, void* partial, int M, int N, int K,
-                   int n_split, int reduce, hipStream_t stream) {
-  const int m_tiles = (M + 15) / 16;
-  const int split = n_split > 1 ? 1 : 0;
-  dim3 grid(N / 64, n_split), block(BLOCK);
-#define DISPATCH(MT)                                                        \
-  do {                                                                      \
-    if (split) {                                                            \
-      hipLaunchKernelGGL((skinny_gemm_kernel<MT, 0, 1>), grid, block, 0,    \
-                         stream, (const bf16*)x, (const bf16*)w, nullptr,   \
-                         (bf16*)out, (float*)partial, M, N, K, n_split);    \
-    } else if (bias) {                                                      \
-      hipLaunchKernelGGL((skinny_gemm_kernel<MT, 1, 0>), grid, block, 0,    \
-                         stream, (const bf16*)x, (const bf16*)w,            \
-                         (const bf16*)bias, (bf16*)out, nullptr, M, N, K,   \
-                         1);                                                \
-    } else {                                                                \
-      hipLaunchKernelGGL((skinny_gemm_kernel<MT, 0, 0>), grid, block, 0,    \
-                         stream, (const bf16*)x, (const bf16*)w, nullptr,   \
-                         (bf16*)out, nullptr, M, N, K, 1);                  \
-    }                                                                       \
-  } while (0)
-  if (m_tiles <= 1) DISPATCH(1);
-  else if (m_tiles <= 2) DISPATCH(2);
-  else if (m_tiles <= 4) DISPATCH(4);
-  else if (m_tiles <= 8) DISPATCH(8);
-  else DISPATCH(16);
-#undef DISPATCH
-  if (split && reduce) {
-    const int64_t MN = (int64_t)M * N;
-    dim3 rgrid((uint32_t)((MN + 255) / 256)), rblock(256);
-    if (bias)
-      hipLaunchKernelGGL((skinny_reduce_kernel<1>), rgrid, rblock, 0, stream,
-                         (const float*)partial, (const bf16*)bias,
-                         (bf16*)out, MN, N, n_split);
-    else
-      hipLaunchKernelGGL((skinny_reduce_kernel<0>), rgrid, rblock, 0, stream,
-                         (const float*)partial, nullptr, (bf16*)out, MN, N,
-                         n_split);
-  }
+template <int MT>
+void skinny_launch_mt(const void* x, const void* w, const void* bias,
+                      void* out, void* partial, int M, int N, int K,
+                      int n_split, hipStream_t stream) {
+  launch_variant(skinny_gemm_kernel<MT, 0, 1>, skinny_gemm_kernel<MT, 1, 0>,
+                 skinny_gemm_kernel<MT, 0, 0>, n_split, bias,
+                 dim3(N / 64, n_split), dim3(BLOCK), stream, x, w, bias, out,
+                 partial, M, N, K, n_split);
 }
 
 }  // namespace
 
 extern "C" {
 
-// partial: scratch [n_split * M * N] floats (only read when n_split > 1).
+// partial: scratch [n_split * M * N] floats (only used when n_split > 1).
+// reduce == 0 leaves the fp32 partials for the consumer to sum (in s
+// order, then bias) — rope_append / rmsnorm read them directly: with
+// n_split > 1 only `partial` is written (bias not applied); with
+// n_split == 1 reduce makes no difference. Serves M <= 64
+// (TL_GEMM_STREAM_M): the binding sends larger M to tl_gemm_tiled and
+// nothing checks it; a larger M here launches nothing and leaves out and
+// partial unwritten.
 void tl_skinny_gemm(const void* x, const void* w, const void* bias,
                     void* out, void* partial, int M, int N, int K,
-                    int n_split, hipStream_t stream) {
-  skinny_launch(x, w, bias, out, partial, M, N, K, n_split, 1, stream);
-}
-
-// Same main kernel, no reduce: with n_split > 1 only `partial`
-// [n_split, M, N] is written (bias not applied); with n_split == 1 this is
-// tl_skinny_gemm.
-void tl_skinny_gemm_partials(const void* x, const void* w, const void* bias,
-                             void* out, void* partial, int M, int N, int K,
-                             int n_split, hipStream_t stream) {
-  skinny_launch(x, w, bias, out, partial, M, N, K, n_split, 0, stream);
+                    int n_split, int reduce, hipStream_t stream) {
+  if (M > TL_GEMM_STREAM_M) return;
+  const int m_tiles = (M + 15) / 16;
+  if (m_tiles <= 1)
+    skinny_launch_mt<1>(x, w, bias, out, partial, M, N, K, n_split, stream);
+  else if (m_tiles <= 2)
+    skinny_launch_mt<2>(x, w, bias, out, partial, M, N, K, n_split, stream);
+  else
+    skinny_launch_mt<4>(x, w, bias, out, partial, M, N, K, n_split, stream);
+  if (n_split > 1 && reduce)
+    launch_splitk_reduce(partial, bias, out, M, N, n_split, stream);
 }
 
 }  // extern "C"
