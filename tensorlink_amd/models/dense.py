@@ -490,23 +490,43 @@ class StageModel(nn.Module):
         w = self.embed_tokens.weight
         return self.embed_tokens(input_ids).to(w.dtype)
 
-    def head(self, hidden: torch.Tensor, pending=None) -> torch.Tensor:
-        """Final norm + lm_head. pending: a last-layer MLP result still to
-        be added to ``hidden`` (forward_carry) — folded into the norm."""
+    def _final_norm(self, hidden: torch.Tensor, pending=None):
+        """pending: a last-layer MLP result still to be added to ``hidden``
+        (forward_carry) — folded into the norm."""
         if pending is None:
-            h = ops.rmsnorm(hidden, self.norm.to(hidden.dtype),
-                            self.config.rms_norm_eps)
-        else:
-            h, _ = ops.add_rmsnorm(pending, hidden,
-                                   self.norm.to(hidden.dtype),
-                                   self.config.rms_norm_eps, rounded=True)
+            return ops.rmsnorm(hidden, self.norm.to(hidden.dtype),
+                               self.config.rms_norm_eps)
+        h, _ = ops.add_rmsnorm(pending, hidden, self.norm.to(hidden.dtype),
+                               self.config.rms_norm_eps, rounded=True)
+        return h
+
+    def _logits(self, h: torch.Tensor) -> torch.Tensor:
         if self.config.tie_word_embeddings and self.has_embedding:
             return h @ self.embed_tokens.weight.t()
         return self.lm_head(h)
 
+    def head(self, hidden: torch.Tensor, pending=None) -> torch.Tensor:
+        """Final norm + lm_head."""
+        return self._logits(self._final_norm(hidden, pending))
+
+    def head_tokens(self, hidden: torch.Tensor, pending=None) -> torch.Tensor:
+        """head(hidden, pending).argmax(-1), int64 [..]. A plain bf16
+        TLLinear head goes through ops.linear_argmax, which skips the
+        logits where the fused kernel serves the shape; anything else — the
+        tied head (a library GEMM, not the family's bits), fp8/fp4, LoRA or
+        TP-sharded heads — takes the logits and their argmax."""
+        h = self._final_norm(hidden, pending)
+        head = getattr(self, "lm_head", None)
+        if type(head) is TLLinear and head.bias is None:
+            return ops.linear_argmax(h, head.weight)
+        return self._logits(h).argmax(-1)
+
     def forward(self, hidden_or_ids, positions, kv_cache: Optional[KVCache]
                 = None, training: bool = False,
-                return_logits: bool = True) -> torch.Tensor:
+                return_logits: bool = True,
+                greedy: bool = False) -> torch.Tensor:
+        """greedy: on a head stage with return_logits, return the argmax
+        tokens (head_tokens) instead of the logits."""
         if self.has_embedding and hidden_or_ids.dtype in (torch.int32,
                                                           torch.int64):
             hidden = self.embed(hidden_or_ids)
@@ -524,6 +544,8 @@ class StageModel(nn.Module):
             if kv_cache is not None:
                 kv_cache.advance(hidden.shape[1])
             if self.has_head and return_logits:
+                if greedy:
+                    return self.head_tokens(hidden, pending)
                 return self.head(hidden, pending)
             # no head here: materialise the stream, so what leaves the
             # stage is what the unfused chain produced
@@ -540,7 +562,7 @@ class StageModel(nn.Module):
         if kv_cache is not None:
             kv_cache.advance(hidden.shape[1])
         if self.has_head and return_logits:
-            return self.head(hidden)
+            return self.head_tokens(hidden) if greedy else self.head(hidden)
         return hidden
 
 

@@ -149,8 +149,13 @@ class Gpt2StageModel(nn.Module):
             return h @ self.wte.weight.t()
         return self.lm_head(h)
 
+    def head_tokens(self, hidden, pending=None):
+        """head(hidden).argmax(-1): this family keeps its logits."""
+        assert pending is None
+        return self.head(hidden).argmax(-1)
+
     def forward(self, hidden_or_ids, positions, kv_cache=None,
-                training=False, return_logits=True):
+                training=False, return_logits=True, greedy=False):
         if self.has_embedding and hidden_or_ids.dtype in (torch.int32,
                                                           torch.int64):
             hidden = self.wte(hidden_or_ids) + self.wpe(positions.long())
@@ -161,7 +166,7 @@ class Gpt2StageModel(nn.Module):
         if kv_cache is not None:
             kv_cache.advance(hidden.shape[1])
         if self.has_head and return_logits:
-            return self.head(hidden)
+            return self.head_tokens(hidden) if greedy else self.head(hidden)
         return hidden
 
 

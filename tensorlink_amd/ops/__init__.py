@@ -521,6 +521,50 @@ def gate_up_swiglu(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     return swiglu_fused(linear(x, weight))
 
 
+# incremented whenever head_argmax.hip picks the tokens (same purpose as
+# gemm_dispatch_count: a silent fallback cannot pass as kernel coverage)
+head_argmax_dispatch_count = 0
+
+# Rows from which the fused head is routed. Below, the fallback's GEMM is
+# the streaming kernel, which does not pay for a 256-row tile and beats the
+# fused pair at M <= 32 (329 vs 256-323 us); M = 48 is a tie within the
+# spread, M = 64 the first measured win (profiles/head_argmax.md).
+HEAD_ARGMAX_M_MIN = 64
+
+
+def _use_head_argmax(M: int, N: int, K: int) -> bool:
+    """The fused greedy head's domain: the wide class, in the family's M
+    range from HEAD_ARGMAX_M_MIN up, where the policy does not split K
+    (always, at the default split target). TL_NO_HEAD_FUSION=1 keeps the
+    GEMM + argmax pair (same tokens) for A/B runs and tests; read per
+    call."""
+    if not (HEAD_ARGMAX_M_MIN <= M and _use_tl_gemm(M, N, K)
+            and _gemm_class(N, K) == "wide"
+            and not _os.environ.get("TL_NO_HEAD_FUSION")):
+        return False
+    ns = _n_split_cache.get((N, K))
+    if ns is None:
+        ns = _n_split_cache[(N, K)] = _require_ext().gemm_n_split(N, K)
+    return ns == 1
+
+
+def linear_argmax(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """linear(x, weight).argmax(-1), int64 [..]: the greedy head. In the
+    fused kernel's domain (head_argmax.hip) the [.., N] logits are never
+    written and the tokens are the same, because every logit there is one
+    K chain with the family's bits. Everything else — CPU, other dtypes,
+    grad enabled, other widths, M outside the routed range — takes the
+    two-step form."""
+    global head_argmax_dispatch_count
+    if _family_input(x):
+        K = x.shape[-1]
+        M = x.numel() // K
+        if _use_head_argmax(M, weight.shape[0], K):
+            head_argmax_dispatch_count += 1
+            return _require_ext().lm_head_argmax(x.contiguous(), weight)
+    return linear(x, weight).argmax(-1)
+
+
 def decode_fusion_enabled() -> bool:
     """False under TL_NO_DECODE_FUSION=1: the decoder then runs the
     unfused chain (every GEMM reduces its own partials, the residual adds

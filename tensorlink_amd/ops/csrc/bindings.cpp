@@ -59,6 +59,8 @@ void tl_gemm_tiled(const void* x, const void* w, const void* bias, void* out,
                    int reduce, hipStream_t stream);
 void tl_gemm_colbal(const void* x, const void* w, void* out, int M, int N,
                     int K, int n_blocks, int fused, hipStream_t stream);
+void tl_head_argmax(const void* x, const void* w, void* best, void* tok,
+                    int M, int N, int K, hipStream_t stream);
 void tl_sample(const void* logits, const void* temps, const void* top_ps,
                const void* top_ks, const void* pres, const void* freqs,
                void* counts, const void* seeds, const void* ctr, void* out,
@@ -549,6 +551,43 @@ Tensor gemm_colbal_swiglu(Tensor x, Tensor w_gate_up, int64_t n_blocks) {
   return gemm_colbal_impl(x, w_gate_up, n_blocks, true);
 }
 
+// Fused greedy head (head_argmax.hip): argmax over N of bf16(x @ W^T) for
+// the wide class where the policy gives n_split == 1, equal to
+// skinny_gemm(x, w).argmax(-1) there. The logits are never written; the
+// only scratch is one packed winner per (256-column panel, row), fully
+// written by the first kernel. Returns int64 with x's leading dimensions.
+// The row limit is ops.GEMM_M_MAX (TL_GEMM_M_MAX, read once as there).
+Tensor lm_head_argmax(Tensor x, Tensor w) {
+  static const int m_max = [] {
+    const char* e = getenv("TL_GEMM_M_MAX");
+    return e ? atoi(e) : 512;
+  }();
+  CHECK_IN(x, torch::kBFloat16);
+  CHECK_IN(w, torch::kBFloat16);
+  TORCH_CHECK(x.dim() >= 1 && w.dim() == 2, "x must be [.., K], w [N, K]");
+  const int64_t K = x.size(-1);
+  const int64_t N = w.size(0);
+  TORCH_CHECK(w.size(1) == K, "K mismatch");
+  TORCH_CHECK(w.device() == x.device(), "operands must share a device");
+  TORCH_CHECK(K >= 32 && K % 32 == 0 && K < (1 << 24), "unsupported K");
+  TORCH_CHECK(N >= TL_GEMM_WIDE_N && N % 64 == 0 && N < (1 << 24),
+              "lm_head_argmax serves the wide class: N >= ", TL_GEMM_WIDE_N,
+              ", N % 64 == 0");
+  TORCH_CHECK(gemm_n_split((int)N, (int)K) == 1,
+              "lm_head_argmax serves only shapes the policy does not split");
+  const int64_t M = x.numel() / K;
+  TORCH_CHECK(M >= 1 && M <= m_max && M < (1 << 24),
+              "lm_head_argmax supports 1 <= M <= ", m_max);
+  auto sizes = x.sizes().vec();
+  sizes.pop_back();
+  auto tok = torch::empty(sizes, x.options().dtype(torch::kLong));
+  auto best = torch::empty({(N + 255) / 256, M},
+                           x.options().dtype(torch::kInt));
+  tl_head_argmax(x.data_ptr(), w.data_ptr(), best.data_ptr(), tok.data_ptr(),
+                 (int)M, (int)N, (int)K, cur_stream());
+  return tok;
+}
+
 // Split-K policy of the MXFP4 kernels: mxfp4_split_for_blocks
 // (gemm_policy.hpp) over the grid before the split.
 static int mxfp4_n_split(int N, int K) {
@@ -764,6 +803,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("gemm_colbal_swiglu", &gemm_colbal_swiglu,
           "column-balanced gate_up GEMM with SwiGLU on the accumulators",
           py::arg("x"), py::arg("w_gate_up"), py::arg("n_blocks") = 0);
+  mod.def("lm_head_argmax", &lm_head_argmax,
+          "fused greedy head: argmax of bf16(x @ W^T) without the logits");
   mod.def("skinny_gemm_partials", &skinny_gemm_partials,
           "decode-M GEMM handing out its fp32 split-K partials");
   mod.def("rmsnorm_add_fwd", &rmsnorm_add_fwd,

@@ -19,6 +19,9 @@
 //   mxfp4_gemm.hip, mxfp4_moe_gemm.hip   slice (mxfp4_k_per), epilogue,
 //                      and the 128-k step body, the same text in both
 // A change to the swizzle or the slice has to be made there too.
+// head_argmax.hip uses the helpers but repeats gemm_tiled_sq_kernel's K loop
+// (staging order, vmcnt count, barriers) as text: a change to that loop has
+// to be made in both, or the fused head stops seeing the family's bits.
 //
 // The helpers take pointers and scalars and own no state, on purpose:
 // guarded accumulator updates send acc[] to scratch, a second __shared__

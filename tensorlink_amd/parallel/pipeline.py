@@ -245,8 +245,13 @@ class PipelineRunner:
                 send_handles.append((self.p2p.isend(hidden, self.next_rank),
                                      hidden))
             else:
-                logits = self.stage.head(hidden[:, -1:]).squeeze(1)
-                tok = self._sample(logits, sp).to(torch.int64)
+                if sp.temperature <= 0:
+                    # greedy: the head hands back tokens (fused where the
+                    # kernel serves the shape, StageModel.head_tokens)
+                    tok = self.stage.head_tokens(hidden[:, -1:]).squeeze(1)
+                else:
+                    logits = self.stage.head(hidden[:, -1:]).squeeze(1)
+                    tok = self._sample(logits, sp).to(torch.int64)
                 if use_events:
                     # event timestamps: no per-chunk host sync (a sync
                     # here exposed kernel-launch gaps and cost ~5%
@@ -317,9 +322,15 @@ class PipelineRunner:
             if not use_graph:
                 for t in range(1, T):
                     pos = positions.unsqueeze(1)
-                    logits = self.stage(cur.unsqueeze(1), pos.int(),
-                                        kv_cache=self.kv_cache).squeeze(1)
-                    cur = self._sample(logits, sp).to(torch.int64)
+                    if sp.temperature <= 0:
+                        cur = self.stage(cur.unsqueeze(1), pos.int(),
+                                         kv_cache=self.kv_cache,
+                                         greedy=True).squeeze(1)
+                    else:
+                        logits = self.stage(
+                            cur.unsqueeze(1), pos.int(),
+                            kv_cache=self.kv_cache).squeeze(1)
+                        cur = self._sample(logits, sp).to(torch.int64)
                     out_tokens[:, t] = cur
                     positions += 1
                     if on_token is not None:
@@ -392,8 +403,12 @@ class PipelineRunner:
                                            self.prev_rank, self.device)
                     hidden = self.stage(hidden, pos, kv_cache=cache,
                                         return_logits=False)
-                    logits = self.stage.head(hidden).squeeze(1)
-                    out_tokens[s:e, step + 1] = self._sample(logits, sp)
+                    if sp.temperature <= 0:
+                        out_tokens[s:e, step + 1] = \
+                            self.stage.head_tokens(hidden).squeeze(1)
+                    else:
+                        logits = self.stage.head(hidden).squeeze(1)
+                        out_tokens[s:e, step + 1] = self._sample(logits, sp)
                 positions[s:e] += 1
         for w, _ in inflight + send_handles:
             w.wait()
@@ -607,13 +622,20 @@ class PipelineRunner:
                         pres=zero, freqs=zero, counter=ctr,
                         seed_base=seed_base)
             else:
-                def pick(logits):
-                    return logits.argmax(-1)
+                pick = None
 
             def step():
-                logits = self.stage(tok_buf.unsqueeze(1),
-                                    pos_buf.unsqueeze(1), kv_cache=cache)
-                tok_buf.copy_(pick(logits.squeeze(1)))
+                if pick is None:
+                    # greedy: the stage returns tokens; where the fused
+                    # head serves the shape no logits are written
+                    tok = self.stage(tok_buf.unsqueeze(1),
+                                     pos_buf.unsqueeze(1), kv_cache=cache,
+                                     greedy=True)
+                    tok_buf.copy_(tok.squeeze(1))
+                else:
+                    logits = self.stage(tok_buf.unsqueeze(1),
+                                        pos_buf.unsqueeze(1), kv_cache=cache)
+                    tok_buf.copy_(pick(logits.squeeze(1)))
                 pos_buf.add_(1)
 
             s = torch.cuda.Stream()
