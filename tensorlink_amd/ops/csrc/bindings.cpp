@@ -448,6 +448,19 @@ static int gemm_n_split(int N, int K) {
   return gemm_n_split_for(N, K, target);
 }
 
+// The [begin, end) of every split for (K, n_split), from the function the
+// kernels slice K with (gemm_k_slice, gemm_policy.hpp): lets a test hold the
+// slice contract against the code itself, with no device involved.
+static std::vector<std::pair<int, int>> gemm_k_slices(int K, int n_split) {
+  TORCH_CHECK(K > 0 && K % 32 == 0 && n_split >= 1, "unsupported shape");
+  std::vector<std::pair<int, int>> out;
+  for (int s = 0; s < n_split; ++s) {
+    const KSlice ks = gemm_k_slice(K, n_split, s);
+    out.emplace_back(ks.begin, ks.end);
+  }
+  return out;
+}
+
 // x @ W^T (+ bias) through the streaming (M <= TL_GEMM_STREAM_M) or tiled
 // kernel. reduce: the bf16 output [.., N]. !reduce: the fp32 split-K
 // partials [n_split, .., N] for a consumer kernel to sum (s order from 0,
@@ -797,6 +810,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("skinny_gemm", &skinny_gemm, "decode-M GEMM: x @ W^T + bias");
   mod.def("gemm_n_split", &gemm_n_split,
           "split-K count the GEMM family's (N,K)-only policy gives");
+  mod.def("gemm_k_slices", &gemm_k_slices,
+          "[(begin, end)] of each split-K slice the GEMM family takes");
   mod.def("gemm_colbal", &gemm_colbal,
           "column-balanced one-pass GEMM: x @ W^T (n_split == 1 shapes)",
           py::arg("x"), py::arg("w"), py::arg("n_blocks") = 0);

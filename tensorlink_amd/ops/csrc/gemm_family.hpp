@@ -4,9 +4,11 @@
 //
 // A row's result is bitwise the same from every bf16 member, at every M,
 // in every batch, because all of them
-//   * step K in fixed chunks from the split's start (family_k_slice), two
-//     mfma_f32_16x16x32_bf16 per 64-k chunk in kk order, f32 accumulators,
-//     a 32-wide tail taking kk = 0 only;
+//   * step K in fixed chunks from the split's start (family_k_slice, which
+//     is gemm_policy.hpp's gemm_k_slice: the splits cover [0, K) exactly,
+//     a 32-wide K tail being the last chunk of the last non-empty split),
+//     two mfma_f32_16x16x32_bf16 per 64-k chunk in kk order, f32
+//     accumulators, a 32-wide tail taking kk = 0 only;
 //   * take the split count from gemm_policy.hpp, pure in (N, K);
 //   * reduce split partials in ascending split order from 0.f, then bias,
 //     then ONE bf16 rounding (splitk_reduce_kernel; the partials consumers
@@ -91,19 +93,16 @@ DEVINLINE bf16x8_t lds_frag(const bf16* tile, int row, int kslot) {
 }
 
 // ---------------------------------------------------------------------------
-// Split-K slice: whole STEP-k chunks, ceil-divided over the splits. Split s
-// covers [s * per, min(K, (s + 1) * per)); a trailing split may be empty
-// and then contributes zeros. SPLIT == 0 is the whole of K.
+// Split-K slice: gemm_k_slice of gemm_policy.hpp, where the bindings and the
+// tests read the same function — whole 64-k chunks, a 32-wide tail counting
+// as one, ceil-divided over the splits, so the slices cover K exactly; a
+// trailing split may be empty and then contributes zeros. SPLIT == 0 is the
+// whole of K.
 // ---------------------------------------------------------------------------
-struct KSlice {
-  int begin, end;
-};
-
-template <int SPLIT, int STEP = 64>
+template <int SPLIT>
 DEVINLINE KSlice family_k_slice(int K, int n_split, int split) {
   if (!SPLIT) return {0, K};
-  const int per = ((K / STEP + n_split - 1) / n_split) * STEP;
-  return {split * per, min(K, split * per + per)};
+  return gemm_k_slice(K, n_split, split);
 }
 
 // ---------------------------------------------------------------------------

@@ -50,6 +50,23 @@ inline int gemm_n_split_for(int N, int K, int target) {
   return n_split;
 }
 
+// Split-K slice SHARED by the streaming and tiled bf16 GEMM kernels, pure
+// in (K, n_split): whole 64-k chunks, ceil-divided over the splits. The
+// bindings accept K % 32 == 0, so the last chunk may be a 32-wide tail; it
+// counts as a chunk ((K + 63) / 64 — a floor here left the tail in no
+// split whenever n_split divided K / 64). Split s covers [begin, end):
+// begins are multiples of 64, the union over s is exactly [0, K), and a
+// trailing split may be empty (end <= begin), contributing zeros.
+struct KSlice {
+  int begin, end;
+};
+
+TL_HD inline KSlice gemm_k_slice(int K, int n_split, int split) {
+  const int per = (((K + 63) / 64 + n_split - 1) / n_split) * 64;
+  const int begin = split * per;
+  return {begin, K < begin + per ? K : begin + per};
+}
+
 // Split-K count of the MXFP4 kernels, counted in their 128-k steps: a
 // column's packed bytes are 4x fewer than bf16, so a split keeps >= 2
 // steps. `blocks` is the grid before the split: N/64 for mxfp4_gemm (pure

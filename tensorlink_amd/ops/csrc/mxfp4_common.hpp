@@ -5,8 +5,8 @@
 // drift apart there: wherever their split counts agree a row is bitwise
 // the same from either. The 128-k step body, the three slice lines and the
 // epilogue are still written out in both kernels: as a shared k loop, and
-// again with only family_k_slice<SPLIT, 128> and store_cfrag_* in their
-// place, the MT = 4 kernels measured 3-5 % slower on the gate_up and
+// again with only a family_k_slice at a 128-k step and store_cfrag_* in
+// their place, the MT = 4 kernels measured 3-5 % slower on the gate_up and
 // Mixtral down shapes (profiles/gemm_family_refactor.md).
 #pragma once
 
@@ -41,10 +41,11 @@ DEVINLINE void mxfp4_build_lut(unsigned char* lut) {
 }
 
 // k range of one split: whole 128-k steps, ceil-divided over the splits
-// (family_k_slice's rule at STEP = 128; see the top of this file for why
-// it is not that call). Split s covers [s * k_per,
-// min(K, (s + 1) * k_per)); a trailing split may be empty and then
-// contributes zeros.
+// (the bf16 family's gemm_k_slice rule in 128-k steps; see the top of this
+// file for why it is not a shared call). The bindings require
+// K % 128 == 0, so K / MX_KSTEP counts every step and the splits cover K.
+// Split s covers [s * k_per, min(K, (s + 1) * k_per)); a trailing split
+// may be empty and then contributes zeros.
 DEVINLINE int mxfp4_k_per(int K, int n_split) {
   const int steps = K / MX_KSTEP;
   return ((steps + n_split - 1) / n_split) * MX_KSTEP;

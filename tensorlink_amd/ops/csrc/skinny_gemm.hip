@@ -45,7 +45,10 @@ __global__ __launch_bounds__(BLOCK, 2) void skinny_gemm_kernel(
 
   const int m_tiles = (M + 15) / 16;
   const int split = SPLIT ? blockIdx.y : 0;
-  const int k_per = SPLIT ? ((K / 64 + n_split - 1) / n_split) * 64 : K;
+  // gemm_k_slice (gemm_policy.hpp) written out: (K + 63) / 64 counts the
+  // 32-wide tail as a chunk, so the splits cover K
+  const int k_per =
+      SPLIT ? (((K + 63) / 64 + n_split - 1) / n_split) * 64 : K;
   const int k_begin = split * k_per;
   const int k_end = min(K, k_begin + k_per);
 
