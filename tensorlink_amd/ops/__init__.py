@@ -731,4 +731,118 @@ causal_lm_loss = ref.causal_lm_loss
 rope_cos_sin = ref.rope_cos_sin
 
 
-chunked_causal_lm_loss = ref.chunked_causal_lm_loss
+# ---------------------------------------------------------------------------
+# Fused linear cross-entropy (training loss head, ops/csrc/head_ce.hip)
+# ---------------------------------------------------------------------------
+# incremented whenever head_ce.hip computes a training loss (same purpose as
+# gemm_dispatch_count: a silent fallback cannot pass as kernel coverage)
+fused_ce_dispatch_count = 0
+
+
+class _LinearCEFn(torch.autograd.Function):
+    """Mean cross-entropy of hidden @ weight^T against labels without the
+    logits. Forward is one pass of the stats kernel over all rows (bf16
+    MFMA, f32 accumulators used unrounded) and a torch sum; nothing syncs
+    the host. Backward walks the rows in chunks: the gradient kernel
+    recomputes a chunk's logits and writes g = dloss/dlogits in bf16, two
+    bf16 library GEMMs turn it into dh and the chunk's share of dW.
+
+    Peak extra memory in backward: one g chunk (chunk * V * 2 B, 1.25 GB at
+    4096 x 152064), dh (N * H * 2 B), and with more than one chunk the fp32
+    dW accumulator plus one chunk's fp32 share (2 * V * H * 4 B, 4.4 GB at
+    the Qwen2.5-7B head); with a single chunk dW comes straight out of the
+    GEMM in the weight's dtype. Forward holds the stats scratch (39 MB at
+    that vocabulary) and two fp32 vectors of N."""
+
+    @staticmethod
+    def forward(ctx, hidden, weight, labels, chunk):
+        C = _require_ext()
+        hidden = hidden.contiguous()
+        weight = weight.contiguous()
+        lse, loss_row = C.head_ce_stats(hidden, weight, labels)
+        valid = (labels >= 0) & (labels < weight.shape[0])
+        ctx.save_for_backward(hidden, weight, labels, lse)
+        ctx.chunk = chunk
+        return loss_row.sum() / valid.sum().clamp(min=1)
+
+    @staticmethod
+    def backward(ctx, dloss):
+        C = _require_ext()
+        hidden, weight, labels, lse = ctx.saved_tensors
+        N = hidden.shape[0]
+        chunk = ctx.chunk
+        valid = (labels >= 0) & (labels < weight.shape[0])
+        # exact +0 for ignored rows: the kernel turns it into zero bits
+        scale = torch.where(valid, dloss.float() / valid.sum().clamp(min=1),
+                            0.0)
+        need_dh, need_dw = ctx.needs_input_grad[:2]
+        dh = torch.empty_like(hidden) if need_dh else None
+        dw = None
+        single = N <= chunk
+        for s in range(0, N, chunk):
+            e = min(s + chunk, N)
+            g = C.head_ce_grad(hidden[s:e], weight, labels[s:e], lse[s:e],
+                               scale[s:e])
+            if need_dh:
+                torch.mm(g, weight, out=dh[s:e])
+            if not need_dw:
+                continue
+            if single:
+                dw = torch.mm(g.t(), hidden[s:e])
+            elif dw is None:
+                dw = torch.mm(g.t(), hidden[s:e], out_dtype=torch.float32)
+            else:
+                dw += torch.mm(g.t(), hidden[s:e], out_dtype=torch.float32)
+        if dw is not None:
+            dw = dw.to(weight.dtype)
+        return dh, dw, None, None
+
+
+def linear_cross_entropy(hidden: torch.Tensor, weight: torch.Tensor,
+                         labels: torch.Tensor, ignore_index: int = -100,
+                         chunk: int = 4096) -> torch.Tensor:
+    """Mean over valid rows of cross_entropy(hidden @ weight^T, labels) as
+    a scalar fp32, on the fused kernels (see :class:`_LinearCEFn`): hidden
+    [N, H] and weight [V, H] bf16 on the GPU with H % 32 == 0, labels [N]
+    int64. A row whose label equals ``ignore_index`` or lies outside
+    [0, V) is ignored; with no valid row the loss is 0. ``chunk`` is the
+    number of rows per backward step. No host sync, so the forward can be
+    captured in a graph."""
+    labels = labels.long()
+    if ignore_index >= 0:
+        labels = torch.where(labels == ignore_index, -100, labels)
+    return _LinearCEFn.apply(hidden, weight, labels.contiguous(), chunk)
+
+
+def _use_fused_ce(hidden: torch.Tensor, weight: torch.Tensor) -> bool:
+    """The fused loss head's domain: bf16 operands on the GPU, H % 32 == 0,
+    extension loaded. TL_NO_FUSED_CE=1 keeps the torch route for A/B runs
+    and tests; read per call."""
+    return (hidden.is_cuda and weight.is_cuda
+            and hidden.dtype == torch.bfloat16
+            and weight.dtype == torch.bfloat16 and _C is not None
+            and hidden.shape[-1] % 32 == 0
+            and not _os.environ.get("TL_NO_FUSED_CE"))
+
+
+def chunked_causal_lm_loss(hidden: torch.Tensor, head_weight: torch.Tensor,
+                           labels: torch.Tensor, chunk: int = 1024,
+                           ignore_index: int = -100) -> torch.Tensor:
+    """Shifted CE loss from the pre-head hidden states, hidden [B,S,H],
+    labels [B,S]: the mean over the valid shifted positions. In the fused
+    kernels' domain (:func:`_use_fused_ce`) it is
+    :func:`linear_cross_entropy` over all B*S rows, each sequence's last
+    position carrying -100, which spares the copy a slice of hidden would
+    make; ``chunk`` then has no part (the fused backward uses its own
+    default). Everything else is ops.reference.chunked_causal_lm_loss,
+    unchanged."""
+    global fused_ce_dispatch_count
+    if not _use_fused_ce(hidden, head_weight):
+        return ref.chunked_causal_lm_loss(hidden, head_weight, labels, chunk,
+                                          ignore_index)
+    fused_ce_dispatch_count += 1
+    B, S, H = hidden.shape
+    lb = torch.full_like(labels, -100)
+    lb[:, :-1] = labels[:, 1:]
+    return linear_cross_entropy(hidden.reshape(B * S, H), head_weight,
+                                lb.reshape(-1), ignore_index)

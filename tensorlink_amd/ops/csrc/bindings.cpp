@@ -61,6 +61,12 @@ void tl_gemm_colbal(const void* x, const void* w, void* out, int M, int N,
                     int K, int n_blocks, int fused, hipStream_t stream);
 void tl_head_argmax(const void* x, const void* w, void* best, void* tok,
                     int M, int N, int K, hipStream_t stream);
+void tl_head_ce_stats(const void* x, const void* w, const void* labels,
+                      void* ms, void* tgt, void* lse, void* loss_row, int M,
+                      int V, int K, int rows_fast, hipStream_t stream);
+void tl_head_ce_grad(const void* x, const void* w, const void* labels,
+                     const void* lse, const void* scale, void* g, int M,
+                     int V, int K, int rows_fast, hipStream_t stream);
 void tl_sample(const void* logits, const void* temps, const void* top_ps,
                const void* top_ks, const void* pres, const void* freqs,
                void* counts, const void* seeds, const void* ctr, void* out,
@@ -601,6 +607,98 @@ Tensor lm_head_argmax(Tensor x, Tensor w) {
   return tok;
 }
 
+// Fused linear cross-entropy (head_ce.hip). x [M, K] and w [V, K] bf16,
+// labels [M] int64; K % 32 == 0, any V >= 1, any M >= 1. The logits are
+// never written. Rows are walked in launches of rows_per_launch (0 = the
+// default) so the stats scratch, one (m, s) float2 per (256-column panel,
+// row) plus one float per row, stays bounded: at the default of 8192 rows
+// it is cdiv(V, 256) * 8192 * 8 B + 32 KB, 39 MB at V = 152064. A row's
+// bits depend on nothing but that row, so they do not depend on
+// rows_per_launch. rows_fast picks the grid order (head_ce.hip) for A/B
+// runs; it does not change a bit either.
+constexpr int64_t HEAD_CE_ROWS_PER_LAUNCH = 8192;
+
+static void head_ce_check(const Tensor& x, const Tensor& w,
+                          const Tensor& labels, int64_t rows_per_launch) {
+  CHECK_IN(x, torch::kBFloat16);
+  CHECK_IN(w, torch::kBFloat16);
+  CHECK_IN(labels, torch::kLong);
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && labels.dim() == 1,
+              "x must be [M, K], w [V, K], labels [M]");
+  TORCH_CHECK(w.size(1) == x.size(1), "K mismatch");
+  TORCH_CHECK(labels.size(0) == x.size(0), "labels must have one per row");
+  TORCH_CHECK(w.device() == x.device() && labels.device() == x.device(),
+              "operands must share a device");
+  const int64_t K = x.size(1);
+  TORCH_CHECK(K >= 32 && K % 32 == 0 && K < (1 << 24), "unsupported K");
+  TORCH_CHECK(w.size(0) >= 1 && w.size(0) < (1 << 24), "unsupported V");
+  TORCH_CHECK(x.size(0) >= 1, "M must be >= 1");
+  TORCH_CHECK(rows_per_launch >= 0 && rows_per_launch < (1 << 24),
+              "rows_per_launch out of range");
+}
+
+std::vector<Tensor> head_ce_stats(Tensor x, Tensor w, Tensor labels,
+                                  int64_t rows_per_launch,
+                                  int64_t rows_fast) {
+  head_ce_check(x, w, labels, rows_per_launch);
+  const int64_t M = x.size(0), K = x.size(1), V = w.size(0);
+  const int64_t rpl = std::min(
+      M, rows_per_launch ? rows_per_launch : HEAD_CE_ROWS_PER_LAUNCH);
+  const int64_t P = (V + 255) / 256;
+  auto f32 = x.options().dtype(torch::kFloat);
+  auto lse = torch::empty({M}, f32);
+  auto loss_row = torch::empty({M}, f32);
+  // [P, rpl] float2 (m, s), then [rpl] label logits
+  auto scratch = torch::empty({P * rpl * 2 + rpl}, f32);
+  float* ms = scratch.data_ptr<float>();
+  float* tgt = ms + P * rpl * 2;
+  for (int64_t r0 = 0; r0 < M; r0 += rpl) {
+    const int64_t rows = std::min(rpl, M - r0);
+    tl_head_ce_stats(
+        static_cast<const char*>(x.data_ptr()) + r0 * K * 2, w.data_ptr(),
+        labels.data_ptr<int64_t>() + r0, ms, tgt,
+        lse.data_ptr<float>() + r0, loss_row.data_ptr<float>() + r0,
+        (int)rows, (int)V, (int)K, (int)rows_fast, cur_stream());
+  }
+  return {lse, loss_row};
+}
+
+Tensor head_ce_grad(Tensor x, Tensor w, Tensor labels, Tensor lse,
+                    Tensor scale, int64_t rows_per_launch, int64_t rows_fast,
+                    c10::optional<Tensor> out) {
+  head_ce_check(x, w, labels, rows_per_launch);
+  CHECK_IN(lse, torch::kFloat);
+  CHECK_IN(scale, torch::kFloat);
+  const int64_t M = x.size(0), K = x.size(1), V = w.size(0);
+  TORCH_CHECK(lse.dim() == 1 && lse.size(0) == M && scale.dim() == 1 &&
+                  scale.size(0) == M,
+              "lse and scale must be [M]");
+  TORCH_CHECK(lse.device() == x.device() && scale.device() == x.device(),
+              "operands must share a device");
+  Tensor g;
+  if (out.has_value()) {
+    g = *out;
+    CHECK_IN(g, torch::kBFloat16);
+    TORCH_CHECK(g.dim() == 2 && g.size(0) == M && g.size(1) == V &&
+                    g.device() == x.device(),
+                "out must be [M, V] on x's device");
+  } else {
+    g = torch::empty({M, V}, x.options());
+  }
+  const int64_t rpl = std::min(
+      M, rows_per_launch ? rows_per_launch : HEAD_CE_ROWS_PER_LAUNCH);
+  for (int64_t r0 = 0; r0 < M; r0 += rpl) {
+    const int64_t rows = std::min(rpl, M - r0);
+    tl_head_ce_grad(
+        static_cast<const char*>(x.data_ptr()) + r0 * K * 2, w.data_ptr(),
+        labels.data_ptr<int64_t>() + r0, lse.data_ptr<float>() + r0,
+        scale.data_ptr<float>() + r0,
+        static_cast<char*>(g.data_ptr()) + r0 * V * 2, (int)rows, (int)V,
+        (int)K, (int)rows_fast, cur_stream());
+  }
+  return g;
+}
+
 // Split-K policy of the MXFP4 kernels: mxfp4_split_for_blocks
 // (gemm_policy.hpp) over the grid before the split.
 static int mxfp4_n_split(int N, int K) {
@@ -820,6 +918,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("x"), py::arg("w_gate_up"), py::arg("n_blocks") = 0);
   mod.def("lm_head_argmax", &lm_head_argmax,
           "fused greedy head: argmax of bf16(x @ W^T) without the logits");
+  mod.def("head_ce_stats", &head_ce_stats,
+          "fused linear cross-entropy, forward: (lse, loss_row) per row",
+          py::arg("x"), py::arg("w"), py::arg("labels"),
+          py::arg("rows_per_launch") = 0, py::arg("rows_fast") = 1);
+  mod.def("head_ce_grad", &head_ce_grad,
+          "fused linear cross-entropy, backward: g = dloss/dlogits in bf16",
+          py::arg("x"), py::arg("w"), py::arg("labels"), py::arg("lse"),
+          py::arg("scale"), py::arg("rows_per_launch") = 0,
+          py::arg("rows_fast") = 1, py::arg("out") = py::none());
   mod.def("skinny_gemm_partials", &skinny_gemm_partials,
           "decode-M GEMM handing out its fp32 split-K partials");
   mod.def("rmsnorm_add_fwd", &rmsnorm_add_fwd,

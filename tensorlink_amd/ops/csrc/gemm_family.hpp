@@ -24,6 +24,8 @@
 // head_argmax.hip uses the helpers but repeats gemm_tiled_sq_kernel's K loop
 // (staging order, vmcnt count, barriers) as text: a change to that loop has
 // to be made in both, or the fused head stops seeing the family's bits.
+// head_ce.hip (fused linear cross-entropy) holds a third copy of the same
+// loop, one text for its two modes: the change goes there too.
 //
 // The helpers take pointers and scalars and own no state, on purpose:
 // guarded accumulator updates send acc[] to scratch, a second __shared__
