@@ -214,10 +214,12 @@ class Attention(nn.Module):
             off = int(kv_cache.seq_lens.max())
             kv_len = off + S
             if table is None:
+                # views of the [B,Hkv,Smax,D] cache: the kernel takes the
+                # strides, nothing is copied
                 k_attn = kv_cache.k[layer_idx][:, :, :kv_len].permute(
-                    0, 2, 1, 3).contiguous()
+                    0, 2, 1, 3)
                 v_attn = kv_cache.v[layer_idx][:, :, :kv_len].permute(
-                    0, 2, 1, 3).contiguous()
+                    0, 2, 1, 3)
             else:
                 k_attn, v_attn = kv_cache.gather_contiguous(layer_idx, kv_len)
             out = ops.attention_prefill(q, k_attn, v_attn, causal=True,

@@ -296,7 +296,8 @@ def attention_prefill(q, k, v, causal: bool = True,
                       scale: Optional[float] = None,
                       q_off: int = 0) -> torch.Tensor:
     """q [B,Sq,Hq,D], k/v [B,Skv,Hkv,D] -> [B,Sq,Hq,D]. Inference path.
-    q_off: query row i is at global position q_off+i (chunked prefill)."""
+    q_off: query row i is at global position q_off+i (chunked prefill).
+    k/v may be views with any batch/token/head strides (D contiguous)."""
     scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
     if not _on_gpu(q):
         return ref.attention_prefill(q, k, v, causal, scale, q_off)
@@ -309,8 +310,14 @@ def attention_prefill(q, k, v, causal: bool = True,
             q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2),
             is_causal=True, scale=scale, enable_gqa=True)
         return out.transpose(1, 2)
-    return _require_ext().prefill_attn(q.contiguous(), k.contiguous(),
-                                       v.contiguous(), scale, causal,
+    # k/v go in as strided views when their last dim is contiguous (the
+    # permuted KV cache): the kernel reads them in place. TL_NO_PREFILL_V3=1
+    # (read per call, in the binding) runs the v2 kernel on copies.
+    if k.stride(-1) != 1:
+        k = k.contiguous()
+    if v.stride(-1) != 1:
+        v = v.contiguous()
+    return _require_ext().prefill_attn(q.contiguous(), k, v, scale, causal,
                                        q_off)
 
 

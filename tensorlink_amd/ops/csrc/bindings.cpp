@@ -4,6 +4,8 @@
 
 #include <torch/extension.h>
 
+#include <cstdlib>
+
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
@@ -35,7 +37,9 @@ void tl_decode_attn(const void* q, const void* k_cache, const void* v_cache,
                     hipStream_t stream);
 void tl_prefill_attn(const void* q, const void* k, const void* v, void* out,
                      int B, int Sq, int Skv, int q_off, int Hq, int Hkv,
-                     int D, float scale, int causal, hipStream_t stream);
+                     int D, float scale, int causal,
+                     const int64_t* k_strides, const int64_t* v_strides,
+                     int use_v3, hipStream_t stream);
 void tl_rope_append(const void* qkv, const void* bias, void* q_out,
                     void* k_cache, void* v_cache, const void* positions,
                     const void* inv_freq, const void* block_table,
@@ -86,7 +90,9 @@ void tl_mxfp4_moe_gemm(const void* x, const void* tok_idx,
 void tl_prefill_attn_lse(const void* q, const void* k, const void* v,
                          void* out, void* lse, int B, int Sq, int Skv,
                          int q_off, int Hq, int Hkv, int D, float scale,
-                         int causal, hipStream_t stream);
+                         int causal, const int64_t* k_strides,
+                         const int64_t* v_strides, int use_v3,
+                         hipStream_t stream);
 void tl_attn_bwd(const void* q, const void* k, const void* v,
                  const void* dout, const void* lse, const void* delta,
                  void* dq, void* dk, void* dv, int B, int S, int Hq,
@@ -309,37 +315,83 @@ Tensor decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor seq_lens,
   return out;
 }
 
+// K/V operands of the prefill kernels: [B,Skv,Hkv,D] views with D
+// contiguous. v3 reads them through their {batch, head, token} strides, so
+// a permuted [B,Hkv,Smax,D] cache view goes in as it is. TL_NO_PREFILL_V3=1
+// (read per call) keeps the v2 kernel, which reads contiguous K/V only, so
+// the copy happens here.
+struct PrefillKV {
+  Tensor k, v;
+  int64_t ks[3], vs[3];
+  int use_v3;
+};
+
+PrefillKV prefill_kv(const Tensor& k_in, const Tensor& v_in) {
+  PrefillKV p;
+  const char* off = std::getenv("TL_NO_PREFILL_V3");
+  p.use_v3 = !(off && *off);
+  for (const Tensor* t : {&k_in, &v_in}) {
+    TORCH_CHECK(t->is_cuda(), "k/v must be on GPU");
+    TORCH_CHECK(t->scalar_type() == torch::kBFloat16, "k/v wrong dtype");
+    TORCH_CHECK(t->dim() == 4, "k/v must be [B,Skv,Hkv,D]");
+  }
+  TORCH_CHECK(k_in.sizes() == v_in.sizes(), "k and v shapes differ");
+  // 16-byte row loads: D contiguous, every other stride a multiple of 8
+  auto direct = [](const Tensor& t) {
+    if (t.size(3) != 1 && t.stride(3) != 1) return false;
+    for (int d = 0; d < 3; ++d)
+      if (t.size(d) != 1 && t.stride(d) % 8 != 0) return false;
+    return t.storage_offset() % 8 == 0;
+  };
+  p.k = (p.use_v3 && direct(k_in)) ? k_in : k_in.contiguous();
+  p.v = (p.use_v3 && direct(v_in)) ? v_in : v_in.contiguous();
+  const Tensor* ts[2] = {&p.k, &p.v};
+  int64_t* ss[2] = {p.ks, p.vs};
+  for (int i = 0; i < 2; ++i) {
+    const Tensor& t = *ts[i];
+    // a size-1 dim's stride is never used: report 0, not what torch kept
+    ss[i][0] = t.size(0) > 1 ? t.stride(0) : 0;
+    ss[i][1] = t.size(2) > 1 ? t.stride(2) : 0;
+    ss[i][2] = t.size(1) > 1 ? t.stride(1) : 0;
+  }
+  return p;
+}
+
 Tensor prefill_attn(Tensor q, Tensor k, Tensor v, double scale, bool causal,
                     int64_t q_off) {
   CHECK_IN(q, torch::kBFloat16);
-  CHECK_IN(k, torch::kBFloat16);
-  CHECK_IN(v, torch::kBFloat16);
+  auto kv = prefill_kv(k, v);
   const int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
   const int Skv = k.size(1);
   const int Hkv = k.size(2);
   TORCH_CHECK(D == 64 || D == 128, "head_dim must be 64 or 128");
+  TORCH_CHECK(k.size(0) == B && k.size(3) == D && Hq % Hkv == 0,
+              "k/v do not match q");
   TORCH_CHECK(q_off + Sq <= Skv || !causal, "q_off + Sq must fit Skv");
   auto out = torch::empty_like(q);
-  tl_prefill_attn(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
-                  B, Sq, Skv, (int)q_off, Hq, Hkv, D, (float)scale,
-                  causal ? 1 : 0, cur_stream());
+  tl_prefill_attn(q.data_ptr(), kv.k.data_ptr(), kv.v.data_ptr(),
+                  out.data_ptr(), B, Sq, Skv, (int)q_off, Hq, Hkv, D,
+                  (float)scale, causal ? 1 : 0, kv.ks, kv.vs, kv.use_v3,
+                  cur_stream());
   return out;
 }
 
 std::vector<Tensor> prefill_attn_lse(Tensor q, Tensor k, Tensor v,
                                      double scale, bool causal) {
   CHECK_IN(q, torch::kBFloat16);
-  CHECK_IN(k, torch::kBFloat16);
-  CHECK_IN(v, torch::kBFloat16);
+  auto kv = prefill_kv(k, v);
   const int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
   const int Skv = k.size(1);
   const int Hkv = k.size(2);
   TORCH_CHECK(D == 64 || D == 128, "head_dim must be 64 or 128");
+  TORCH_CHECK(k.size(0) == B && k.size(3) == D && Hq % Hkv == 0,
+              "k/v do not match q");
   auto out = torch::empty_like(q);
   auto lse = torch::empty({B, Hq, Sq}, q.options().dtype(torch::kFloat));
-  tl_prefill_attn_lse(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+  tl_prefill_attn_lse(q.data_ptr(), kv.k.data_ptr(), kv.v.data_ptr(),
                       out.data_ptr(), lse.data_ptr(), B, Sq, Skv, 0, Hq,
-                      Hkv, D, (float)scale, causal ? 1 : 0, cur_stream());
+                      Hkv, D, (float)scale, causal ? 1 : 0, kv.ks, kv.vs,
+                      kv.use_v3, cur_stream());
   return {out, lse};
 }
 

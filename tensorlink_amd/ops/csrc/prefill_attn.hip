@@ -213,22 +213,47 @@ __global__ __launch_bounds__(BLOCK) void prefill_attn_kernel(
 
 extern "C" {
 
+// v3 (prefill_attn_v3.hip): same bits, pipelined, K/V read through strides.
+void tl_prefill_attn_v3(const void* q, const void* k, const void* v,
+                        void* out, void* lse, int B, int Sq, int Skv,
+                        int q_off, int Hq, int Hkv, int D, float scale,
+                        int causal, int64_t k_sb, int64_t k_sh, int64_t k_ss,
+                        int64_t v_sb, int64_t v_sh, int64_t v_ss,
+                        hipStream_t stream);
+
+// k_strides / v_strides = {batch, head, token} strides in elements of the
+// [B,Skv,Hkv,D] views (D contiguous). use_v3 = 0 runs the v2 kernel above,
+// which reads contiguous K/V only and ignores the strides: the caller
+// copies first (bindings.cpp does).
 void tl_prefill_attn_lse(const void* q, const void* k, const void* v,
                          void* out, void* lse, int B, int Sq, int Skv,
                          int q_off, int Hq, int Hkv, int D, float scale,
-                         int causal, hipStream_t stream);
+                         int causal, const int64_t* k_strides,
+                         const int64_t* v_strides, int use_v3,
+                         hipStream_t stream);
 
 void tl_prefill_attn(const void* q, const void* k, const void* v, void* out,
                      int B, int Sq, int Skv, int q_off, int Hq, int Hkv,
-                     int D, float scale, int causal, hipStream_t stream) {
+                     int D, float scale, int causal,
+                     const int64_t* k_strides, const int64_t* v_strides,
+                     int use_v3, hipStream_t stream) {
   tl_prefill_attn_lse(q, k, v, out, nullptr, B, Sq, Skv, q_off, Hq, Hkv, D,
-                      scale, causal, stream);
+                      scale, causal, k_strides, v_strides, use_v3, stream);
 }
 
 void tl_prefill_attn_lse(const void* q, const void* k, const void* v,
                          void* out, void* lse, int B, int Sq, int Skv,
                          int q_off, int Hq, int Hkv, int D, float scale,
-                         int causal, hipStream_t stream) {
+                         int causal, const int64_t* k_strides,
+                         const int64_t* v_strides, int use_v3,
+                         hipStream_t stream) {
+  if (use_v3) {
+    tl_prefill_attn_v3(q, k, v, out, lse, B, Sq, Skv, q_off, Hq, Hkv, D,
+                       scale, causal, k_strides[0], k_strides[1],
+                       k_strides[2], v_strides[0], v_strides[1],
+                       v_strides[2], stream);
+    return;
+  }
   dim3 grid((Sq + BM - 1) / BM, Hq, B), block(BLOCK);
   if (D == 128)
     hipLaunchKernelGGL((prefill_attn_kernel<128>), grid, block, 0, stream,
