@@ -21,11 +21,19 @@
 //   mxfp4_gemm.hip, mxfp4_moe_gemm.hip   slice (mxfp4_k_per), epilogue,
 //                      and the 128-k step body, the same text in both
 // A change to the swizzle or the slice has to be made there too.
-// head_argmax.hip uses the helpers but repeats gemm_tiled_sq_kernel's K loop
-// (staging order, vmcnt count, barriers) as text: a change to that loop has
-// to be made in both, or the fused head stops seeing the family's bits.
-// head_ce.hip (fused linear cross-entropy) holds a third copy of the same
-// loop, one text for its two modes: the change goes there too.
+//
+// The 256x256-tile K loop is sq256_k_loop below: the two fused heads
+// (head_argmax.hip, head_ce.hip; three kernels) call it, and their per-row
+// reduce over a panel is sq256_row_reduce. gemm_tiled_sq_kernel still
+// writes the same loop out, because calling the helper made it 0.5 - 0.8 %
+// slower at the lm_head shape with the loop's instructions unchanged
+// (profiles/sq256_loop_refactor.md §4): a change to that loop has to be
+// made in gemm_tiled.hip too, or the heads stop seeing the family's bits.
+// gemm_tiled_kernel<MT> keeps a loop
+// of its own, the same shape with other constants: as one template
+// with this one it lost 4 VGPRs at MT = 8 and gained an s_waitcnt at MT =
+// 16 (profiles/sq256_loop_refactor.md §0), and a template is not kept for
+// one shape.
 //
 // The helpers take pointers and scalars and own no state, on purpose:
 // guarded accumulator updates send acc[] to scratch, a second __shared__
@@ -132,6 +140,147 @@ DEVINLINE void store_cfrag_bf16(f32x4 c, bf16* base, int row0, int row_end,
     const int row = row0 + quad * 4 + r;
     if (row < row_end) base[(int64_t)row * ld + col] = f2bf(c[r]);
   }
+}
+
+// ---------------------------------------------------------------------------
+// The 256x256-tile K loop: acc = x[m_base .. +256, ks] @ w[n_base .. +256,
+// ks]^T, from zeroed accumulators. 512 threads, 8 waves as 2(M) x 4(N)
+// quadrants of 128 x 64; lane (col, quad) of wave (wm, wn) ends with
+//   acc[mt * 4 + nt][r] = C[wm*128 + mt*16 + quad*4 + r][wn*64 + nt*16 + col]
+// `lds` is the calling kernel's one shared object, used as a double buffer
+// of [256 x rows + 256 W rows][64 k] swizzled images, all staged by glds:
+// each wave issues 4 x pieces and 4 W pieces per tile, waits for its own
+// tile-t loads with vmcnt(8) while tile t+1's stay in flight, and the raw
+// barrier aligns the workgroup. x rows are clamped to M - 1 and W rows to
+// N - 1: rows >= M and columns >= N of the tile hold duplicates, for the
+// caller to leave out. On return every wave is past the last fragment read
+// and no glds is in flight, so the caller may reuse `lds`.
+// head_argmax_kernel and head_ce_kernel are this loop plus an epilogue, and
+// gemm_tiled_sq_kernel is the same text plus its store, which is why the
+// fused heads see the family's bits.
+// The caller passes its own `lane` (threadIdx.x & 63) and `wave`
+// (threadIdx.x >> 6).
+// ---------------------------------------------------------------------------
+DEVINLINE void sq256_k_loop(const bf16* __restrict__ x,
+                            const bf16* __restrict__ w, int m_base,
+                            int n_base, int M, int N, int K, KSlice ks,
+                            bf16 (&lds)[2][256 + 256][64],
+                            f32x4 (&acc)[32], int lane, int wave) {
+  const int col = lane & 15;
+  const int quad = lane >> 4;
+  const int wm = wave >> 2;                   // 0..1: 128-row band
+  const int wn = wave & 3;                    // 0..3: 64-col band
+  const int l8 = lane >> 3;
+
+#pragma unroll
+  for (int m = 0; m < 32; ++m) acc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  // x: 32 pieces of 8 rows -> 4 per wave; W: 32 pieces -> 4 per wave
+  auto stage = [&](int bufi, int k0) {
+    if (k0 >= ks.end) return;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int piece = wave * 4 + g;
+      const int xr = min(m_base + piece * 8 + l8, M - 1);
+      stage_8x64(x + (int64_t)xr * K, lane, k0, K, &lds[bufi][piece * 8][0]);
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int wpiece = wave * 4 + g;
+      const int gr = min(n_base + wpiece * 8 + l8, N - 1);
+      stage_8x64(w + (int64_t)gr * K, lane, k0, K,
+                 &lds[bufi][256 + wpiece * 8][0]);
+    }
+  };
+
+  stage(0, ks.begin);
+  int buf = 0;
+  for (int k0 = ks.begin; k0 < ks.end; k0 += 64) {
+    if (k0 + 64 < ks.end) {
+      stage(buf ^ 1, k0 + 64);                // in flight under compute
+      waitcnt_vm<8>();                        // tile t landed; t+1 out
+    } else {
+      waitcnt_vm<0>();                        // last tile: drain
+    }
+    __builtin_amdgcn_s_barrier();
+    const int tile_k = min(64, ks.end - k0);
+    const bf16* xt = &lds[buf][0][0];
+    const bf16* wt = &lds[buf][256][0];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      if (kk * 32 < tile_k) {
+        bf16x8_t bfrag[4], afrag[8];
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+          bfrag[nt] = lds_frag(wt, wn * 64 + nt * 16 + col, kk * 4 + quad);
+#pragma unroll
+        for (int mt = 0; mt < 8; ++mt)
+          afrag[mt] = lds_frag(xt, wm * 128 + mt * 16 + col, kk * 4 + quad);
+#pragma unroll
+        for (int mt = 0; mt < 8; ++mt)
+#pragma unroll
+          for (int nt = 0; nt < 4; ++nt)
+            acc[mt * 4 + nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                afrag[mt], bfrag[nt], acc[mt * 4 + nt], 0, 0, 0);
+      }
+    }
+    // all waves done reading buf before the next iteration's glds overwrite
+    // it
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    buf ^= 1;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Row reduce over the 256 columns of a sq256_k_loop tile, for the fused
+// heads. val(mt, r, nt) is the calling lane's value for accumulator element
+// acc[mt * 4 + nt][r] (`init` for a column that takes no part); op combines
+// two values. Fixed order per row: the lane's nt = 0..3 from `init`, then
+// the 16 lanes of the column group by xor offsets 1, 2, 4, 8 — lane `col`
+// keeps rows col and col + 16 of the group's 32 (index mt * 4 + r) — then
+// the four wn waves meet in `red`, a [4 wn][256 rows] image in the freed
+// LDS, and thread t < 256 returns ((r0 op r1) op r2) op r3 of tile row t.
+// Threads >= 256 return `init`. Ends behind a __syncthreads; a second call
+// on the same `red` needs one more in between.
+// ---------------------------------------------------------------------------
+template <typename T, typename Val, typename Op>
+DEVINLINE T sq256_row_reduce(T* red, T init, Val val, Op op) {
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int col = lane & 15;
+  const int quad = lane >> 4;
+  const int wm = wave >> 2;
+  const int wn = wave & 3;
+
+  T keep[2] = {init, init};
+#pragma unroll
+  for (int mt = 0; mt < 8; ++mt) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      T v = init;
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) v = op(v, val(mt, r, nt));
+#pragma unroll
+      for (int off = 1; off < 16; off <<= 1)
+        v = op(v, __shfl_xor(v, off, WAVE_SIZE));
+      if (((mt * 4 + r) & 15) == col) keep[(mt * 4 + r) >> 4] = v;
+    }
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int idx = h * 16 + col;             // = mt * 4 + r
+    const int row = wm * 128 + (idx >> 2) * 16 + quad * 4 + (idx & 3);
+    red[wn * 256 + row] = keep[h];
+  }
+  __syncthreads();
+  T out = init;
+  if (threadIdx.x < 256) {
+    const int row = threadIdx.x;
+    out = op(op(op(red[row], red[256 + row]), red[512 + row]),
+             red[768 + row]);
+  }
+  return out;
 }
 
 // Launch the variant of a <HAS_BIAS, SPLIT> kernel that a call needs: the

@@ -152,6 +152,11 @@ __global__ __launch_bounds__(BLOCK, 2) void gemm_tiled_kernel(
 // work (256 mfma/block) is also long enough to hide the glds latency
 // that starves the small-tile kernels. Handles N % 256 != 0 (lm_head
 // 151936) with clamped W loads + guarded stores.
+// The K loop below is sq256_k_loop (gemm_family.hpp), which the fused
+// heads call, written out: called from here it cost this kernel 2 us in
+// 350 at the lm_head shape (profiles/sq256_loop_refactor.md). The two
+// texts are to be kept equal; tests/test_head_argmax_gpu.py and
+// tests/test_fused_ce_gpu.py compare the heads with this kernel bit for bit.
 template <int HAS_BIAS, int SPLIT>
 __global__ __launch_bounds__(512, 1) void gemm_tiled_sq_kernel(
     const bf16* __restrict__ x,     // [M, K]

@@ -12,12 +12,11 @@
 // per (panel, row) and one float per row, fully written before it is read
 // (no atomics, no pre-zeroing, no host sync).
 //
-// The K loop is gemm_tiled_sq_kernel's (gemm_tiled.hip), repeated as text a
-// third time (head_argmax.hip holds the second copy): 256x256 tile, 8 waves
-// as 2(M) x 4(N), 128 KB LDS in one object, all-glds staging, counted
-// vmcnt, raw barriers, clamped W rows for V % 256 != 0 and clamped x rows
-// for the last row block. One copy serves both modes. Do not change it here
-// without changing it there.
+// The accumulators come from sq256_k_loop (gemm_family.hpp), the 256x256
+// loop gemm_tiled_sq_kernel writes out and head_argmax_kernel calls, in
+// both modes: a logit here has the bits the family's GEMM would round.
+// MODE 0's two row passes (max, then sum of exp) are sq256_row_reduce, which fixes the order
+// of the float sum.
 //
 // Ghosts: the clamped loads duplicate W row V - 1 into columns >= V of the
 // last panel and x row M - 1 into rows >= M of the last row block. Ghost
@@ -61,69 +60,10 @@ __global__ __launch_bounds__(512, 1) void head_ce_kernel(
                            : (int)blockIdx.x / n_panel;
   const int m_base = rb * 256;
 
-  const KSlice ks = family_k_slice<0>(K, 1, 0);
-
   __shared__ bf16 lds[2][256 + 256][64];
-
   f32x4 acc[32];
-#pragma unroll
-  for (int m = 0; m < 32; ++m) acc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  const int l8 = lane >> 3;
-
-  // x: 32 pieces of 8 rows -> 4 per wave; W: 32 pieces -> 4 per wave
-  auto stage = [&](int bufi, int k0) {
-    if (k0 >= ks.end) return;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int piece = wave * 4 + p;
-      const int xr = min(m_base + piece * 8 + l8, M - 1);
-      stage_8x64(x + (int64_t)xr * K, lane, k0, K, &lds[bufi][piece * 8][0]);
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int wpiece = wave * 4 + p;
-      const int gr = min(panel * 256 + wpiece * 8 + l8, V - 1);
-      stage_8x64(w + (int64_t)gr * K, lane, k0, K,
-                 &lds[bufi][256 + wpiece * 8][0]);
-    }
-  };
-
-  stage(0, ks.begin);
-  int buf = 0;
-  for (int k0 = ks.begin; k0 < ks.end; k0 += 64) {
-    if (k0 + 64 < ks.end) {
-      stage(buf ^ 1, k0 + 64);
-      waitcnt_vm<8>();                        // tile t landed; t+1 out
-    } else {
-      waitcnt_vm<0>();
-    }
-    __builtin_amdgcn_s_barrier();
-    const int tile_k = min(64, ks.end - k0);
-    const bf16* xt = &lds[buf][0][0];
-    const bf16* wt = &lds[buf][256][0];
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      if (kk * 32 < tile_k) {
-        bf16x8_t bfrag[4], afrag[8];
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-          bfrag[nt] = lds_frag(wt, wn * 64 + nt * 16 + col, kk * 4 + quad);
-#pragma unroll
-        for (int mt = 0; mt < 8; ++mt)
-          afrag[mt] = lds_frag(xt, wm * 128 + mt * 16 + col, kk * 4 + quad);
-#pragma unroll
-        for (int mt = 0; mt < 8; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt)
-            acc[mt * 4 + nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                afrag[mt], bfrag[nt], acc[mt * 4 + nt], 0, 0, 0);
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    buf ^= 1;
-  }
+  sq256_k_loop(x, w, m_base, panel * 256, M, V, K,
+               family_k_slice<0>(K, 1, 0), lds, acc, lane, wave);
 
   // Epilogue. Lane (col, quad) holds C[mt*16 + quad*4 + r][nt*16 + col] of
   // its wave's 128 x 64 quadrant. gc0 is the global column of nt = 0; a
@@ -132,63 +72,39 @@ __global__ __launch_bounds__(512, 1) void head_ce_kernel(
   const int lrow0 = wm * 128 + quad * 4;      // + mt * 16 + r: row in tile
 
   if constexpr (MODE == 0) {
-    // The 4 wn waves of a row meet in LDS: the ring is free (the loop's
-    // last barrier is behind every wave's last fragment read, and its
-    // vmcnt(0) left no glds in flight). red: [4 wn][256 rows] partials,
-    // then [256] the panel's row maxima.
+    // The freed LDS ring: red is sq256_row_reduce's [4 wn][256 rows]
+    // meeting place, pmax [256] the panel's row maxima.
     float* red = reinterpret_cast<float*>(&lds[0][0][0]);
     float* pmax = red + 4 * 256;
 
-    // 1) row max: the lane's 4 nt registers, then the 16 lanes of the
-    // column group; lane `col` keeps rows col and col + 16 of the group's
-    // 32 (index mt*4 + r), as head_argmax does.
-    float keep[2] = {0.f, 0.f};
+    // 1) row max. Every panel has a real column, so it is finite for
+    // finite data.
+    const float pm = sq256_row_reduce(
+        red, -INFINITY,
+        [&](int mt, int r, int nt) {
+          return gc0 + nt * 16 < V ? acc[mt * 4 + nt][r] : -INFINITY;
+        },
+        [](float a, float b) { return fmaxf(a, b); });
+    if (threadIdx.x < 256) pmax[threadIdx.x] = pm;
+    __syncthreads();
+
+    // 2) s = sum exp(logit - panel max), in the helper's fixed order.
+    const float s = sq256_row_reduce(
+        red, 0.f,
+        [&](int mt, int r, int nt) {
+          const float e = expf(acc[mt * 4 + nt][r] - pmax[lrow0 + mt * 16 + r]);
+          return gc0 + nt * 16 < V ? e : 0.f;
+        },
+        [](float a, float b) { return a + b; });
+    if (threadIdx.x < 256 && m_base + threadIdx.x < M)
+      ms_out[(int64_t)panel * M + m_base + threadIdx.x] = make_float2(pm, s);
+
+    // The label logit, from the one lane whose column is the label.
 #pragma unroll
     for (int mt = 0; mt < 8; ++mt) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        float v = -INFINITY;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-          v = fmaxf(v, gc0 + nt * 16 < V ? acc[mt * 4 + nt][r] : -INFINITY);
-#pragma unroll
-        for (int off = 1; off < 16; off <<= 1)
-          v = fmaxf(v, __shfl_xor(v, off, WAVE_SIZE));
-        if (((mt * 4 + r) & 15) == col) keep[(mt * 4 + r) >> 4] = v;
-      }
-    }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int idx = h * 16 + col;           // = mt * 4 + r
-      red[wn * 256 + lrow0 + (idx >> 2) * 16 + (idx & 3)] = keep[h];
-    }
-    __syncthreads();
-    if (threadIdx.x < 256) {
-      const int row = threadIdx.x;
-      // every panel has a real column, so this is finite for finite data
-      pmax[row] = fmaxf(fmaxf(red[row], red[256 + row]),
-                        fmaxf(red[512 + row], red[768 + row]));
-    }
-    __syncthreads();
-
-    // 2) s = sum exp(logit - panel max), nt order, then the xor tree; and
-    // the label logit from the one lane whose column is the label.
-#pragma unroll
-    for (int mt = 0; mt < 8; ++mt) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int lrow = lrow0 + mt * 16 + r;
-        const float pm = pmax[lrow];
-        float s = 0.f;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-          s += gc0 + nt * 16 < V ? expf(acc[mt * 4 + nt][r] - pm) : 0.f;
-#pragma unroll
-        for (int off = 1; off < 16; off <<= 1)
-          s += __shfl_xor(s, off, WAVE_SIZE);
-        if (((mt * 4 + r) & 15) == col) keep[(mt * 4 + r) >> 4] = s;
-
-        const int row = m_base + lrow;
+        const int row = m_base + lrow0 + mt * 16 + r;
         const int64_t lab = labels[min(row, M - 1)];
         const int64_t d = lab - gc0;          // 0, 16, 32, 48: nt * 16
         if (row < M && d >= 0 && d < 64 && (d & 15) == 0 && lab < V) {
@@ -198,20 +114,6 @@ __global__ __launch_bounds__(512, 1) void head_ce_kernel(
           tgt[row] = nt < 2 ? a01 : a23;
         }
       }
-    }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int idx = h * 16 + col;
-      red[wn * 256 + lrow0 + (idx >> 2) * 16 + (idx & 3)] = keep[h];
-    }
-    __syncthreads();
-    if (threadIdx.x < 256) {
-      const int row = threadIdx.x;
-      const float s = ((red[row] + red[256 + row]) + red[512 + row]) +
-                      red[768 + row];
-      if (m_base + row < M)
-        ms_out[(int64_t)panel * M + m_base + row] =
-            make_float2(pmax[row], s);
     }
   } else {
 #pragma unroll

@@ -14,6 +14,10 @@ trailing splits, and at every M template (streaming MT 1 / 2 / 4, tiled MT
 * bitwise: a row is the same at every M, a call repeats, and the partials
   reduced on the host in the contract's order are ops.linear's bits.
 
+The 256x256 kernel (N >= WIDE_N, M >= 65) splits no small K, so it has a
+test of its own at the end, at n_split == 1: the same three kinds of check,
+the bitwise one against the streaming kernel, which shares no loop with it.
+
 tests/test_gemm_family_cpu.py shows that wrong kernels fail the first two.
 Every call asserts that the hand-written family served it and that the
 policy split K the way the table says, so neither a fallback nor a changed
@@ -72,10 +76,12 @@ def _reference(N, K, bias):
     return ref, emu
 
 
-def _family(fn_name, N, K, x, w, b=None):
+def _family(fn_name, N, K, x, w, b=None, n_split=None):
     """ops.linear / ops.linear_partials with the two per-call asserts."""
     ops = _ops()
-    assert _ext().gemm_n_split(N, K) == fo.SHAPES[(N, K)], \
+    if n_split is None:
+        n_split = fo.SHAPES[(N, K)]
+    assert _ext().gemm_n_split(N, K) == n_split, \
         "the policy no longer splits this shape as the table says"
     before = ops.gemm_dispatch_count
     out = getattr(ops, fn_name)(x, w, b)
@@ -83,8 +89,8 @@ def _family(fn_name, N, K, x, w, b=None):
     return out
 
 
-def _linear(N, K, x, w, b=None):
-    out = _family("linear", N, K, x, w, b)
+def _linear(N, K, x, w, b=None, n_split=None):
+    out = _family("linear", N, K, x, w, b, n_split)
     assert out.dtype == torch.bfloat16 and out.shape == (x.shape[0], N)
     return out
 
@@ -220,3 +226,55 @@ def test_k_slices_of_the_code_are_the_contract():
         for n_split in (1, 2, 4, 8, 16):
             got = [tuple(s) for s in C.gemm_k_slices(K, n_split)]
             assert got == fo.k_slices(K, n_split), (K, n_split)
+
+
+# --------------------------------------------------------------------------
+# the 256x256 kernel, against oracles that share no code with it
+# --------------------------------------------------------------------------
+# full panels with one chunk; a half-empty last panel with a K tail;
+# prologue, steady state and drain with a quarter-full last panel
+SQ_SHAPES = ((65536, 64), (65664, 96), (65600, 192))
+# one row block with ghost rows, a full one, two
+SQ_MS = (65, 256, 257)
+
+
+@functools.lru_cache(maxsize=None)
+def _sq_case(N, K):
+    c = ko.gemm_case(max(SQ_MS), N, K, True)
+    return {k: v.to(DEV) for k, v in c.items()}
+
+
+@pytest.mark.parametrize("bias", [False, True])
+@pytest.mark.parametrize("N,K", SQ_SHAPES)
+def test_sq256_kernel_against_streaming_fp64_and_onehot(N, K, bias):
+    """gemm_tiled_sq_kernel, and with it the K loop the fused heads call:
+    the head tests compare those against this kernel, so it is held here
+    against the streaming kernel's rows (bitwise), float64 (the conformance
+    rule) and columns of W (one-hot rows, exact)."""
+    assert N >= fo.WIDE_N and min(SQ_MS) > fo.STREAM_M
+    c = _sq_case(N, K)
+    x, w = c["x"], c["w"]
+    b = c["b"] if bias else None
+
+    def lin(x_rows):
+        """ops.linear: the 256x256 kernel above 64 rows, the streaming
+        kernel up to 64."""
+        return _linear(N, K, x_rows, w, b, n_split=1)
+
+    def streamed(x_rows):
+        return torch.cat([lin(x_rows[r0:r0 + fo.STREAM_M].contiguous())
+                          for r0 in range(0, x_rows.shape[0], fo.STREAM_M)])
+
+    want = streamed(x)
+    ref = ko.linear(x, w, b)
+    emu = ko.bf16_round(ko.linear(x, w, b, dtype=torch.float32))
+    ks = fo.onehot_ks(K, fo.k_slices(K, 1))
+    for M in SQ_MS:
+        out = lin(x[:M].contiguous())
+        assert torch.equal(out, want[:M]), \
+            f"M={M}: rows differ from the streaming kernel's"
+        check(f"gemm sq256 N{N} K{K} M{M} bias{int(bias)}", out, ref[:M],
+              ko.nme(emu[:M], ref[:M]))
+        hot = fo.onehot_rows(M, K, ks).to(DEV)
+        assert fo.bits_equal(lin(hot), fo.onehot_expected(w, b, M, ks)), \
+            f"M={M}: linear(one-hot) is not w[:, k]"
