@@ -321,6 +321,64 @@ def attention_prefill(q, k, v, causal: bool = True,
                                        q_off)
 
 
+# incremented whenever the carried-state kernel handles a chunk (same
+# purpose as gemm_dispatch_count: a silent fallback to torch math cannot
+# pass as kernel coverage)
+attn_carry_dispatch_count = 0
+
+
+class AttnCarry:
+    """The online-softmax state :func:`attention_prefill_carry` carries
+    between key chunks, fp32, updated in place: ``o`` [B,Sq,Hq,D] is the
+    unnormalised accumulator, ``ml`` [B,Hq,Sq,2] the (max, sum) pair per
+    row."""
+
+    __slots__ = ("o", "ml")
+
+    def __init__(self, o: torch.Tensor, ml: torch.Tensor):
+        self.o = o
+        self.ml = ml
+
+    @classmethod
+    def empty(cls, q: torch.Tensor) -> "AttnCarry":
+        """Uninitialised state for q [B,Sq,Hq,D]; the ``first`` call does
+        not read it."""
+        B, Sq, Hq, D = q.shape
+        return cls(torch.empty(B, Sq, Hq, D, dtype=torch.float32,
+                               device=q.device),
+                   torch.empty(B, Hq, Sq, 2, dtype=torch.float32,
+                               device=q.device))
+
+
+def attention_prefill_carry(q, k, v, carry: AttnCarry, *, causal: bool,
+                            q_off: int = 0, scale: Optional[float] = None,
+                            first: bool, last: bool):
+    """Attention of q [B,Sq,Hq,D] over ONE key chunk k/v [B,Skv,Hkv,D] of a
+    longer key sequence, with the online-softmax state in ``carry``. The
+    state is not read when ``first`` and is updated in place unless
+    ``last``; the ``last`` call returns the normalised [B,Sq,Hq,D] output,
+    the others None. With ``causal``, key j of this chunk is visible to
+    query row i when j <= q_off + i. Chunks may come in any order; in
+    ascending order with boundaries on multiples of 64 keys the result is
+    bit-identical to one prefill kernel call over the concatenation.
+    GPU bf16 at head dim 64 / 128 runs the carried-state prefill kernel,
+    everything else the fp32 reference."""
+    global attn_carry_dispatch_count
+    scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    if (q.is_cuda and q.dtype == torch.bfloat16
+            and q.shape[-1] in (64, 128)):
+        C = _require_ext()        # a missing kernel is an error, not a
+        if k.stride(-1) != 1:     # reason to run torch math on the GPU
+            k = k.contiguous()
+        if v.stride(-1) != 1:
+            v = v.contiguous()
+        attn_carry_dispatch_count += 1
+        return C.prefill_attn_carry(q.contiguous(), k, v, carry.o, carry.ml,
+                                    scale, causal, q_off, first, last)
+    return ref.attention_prefill_carry(q, k, v, carry.o, carry.ml, causal,
+                                       scale, q_off, first, last)
+
+
 class _FlashAttnFn(torch.autograd.Function):
     """Hand-written flash attention for training (gfx950): forward =
     prefill kernel saving the logsumexp; backward = the two MFMA kernels

@@ -93,6 +93,13 @@ void tl_prefill_attn_lse(const void* q, const void* k, const void* v,
                          int causal, const int64_t* k_strides,
                          const int64_t* v_strides, int use_v3,
                          hipStream_t stream);
+void tl_prefill_attn_carry(const void* q, const void* k, const void* v,
+                           void* out, void* lse, void* o_state,
+                           void* ml_state, int B, int Sq, int Skv, int q_off,
+                           int Hq, int Hkv, int D, float scale, int causal,
+                           int first, int last, int64_t k_sb, int64_t k_sh,
+                           int64_t k_ss, int64_t v_sb, int64_t v_sh,
+                           int64_t v_ss, hipStream_t stream);
 void tl_attn_bwd(const void* q, const void* k, const void* v,
                  const void* dout, const void* lse, const void* delta,
                  void* dq, void* dk, void* dv, int B, int S, int Hq,
@@ -326,10 +333,11 @@ struct PrefillKV {
   int use_v3;
 };
 
-PrefillKV prefill_kv(const Tensor& k_in, const Tensor& v_in) {
+PrefillKV prefill_kv(const Tensor& k_in, const Tensor& v_in,
+                     bool v3_only = false) {
   PrefillKV p;
   const char* off = std::getenv("TL_NO_PREFILL_V3");
-  p.use_v3 = !(off && *off);
+  p.use_v3 = v3_only || !(off && *off);
   for (const Tensor* t : {&k_in, &v_in}) {
     TORCH_CHECK(t->is_cuda(), "k/v must be on GPU");
     TORCH_CHECK(t->scalar_type() == torch::kBFloat16, "k/v wrong dtype");
@@ -393,6 +401,55 @@ std::vector<Tensor> prefill_attn_lse(Tensor q, Tensor k, Tensor v,
                       Hkv, D, (float)scale, causal ? 1 : 0, kv.ks, kv.vs,
                       kv.use_v3, cur_stream());
   return {out, lse};
+}
+
+// One key chunk of a carried online softmax (prefill_attn_v3.hip, CARRY):
+// o_state [B,Sq,Hq,D] and ml_state [B,Hq,Sq,2] are the caller's fp32 state,
+// read unless `first`, written in place unless `last`. Returns None, or on
+// `last` out (bf16), or (out, lse) with want_lse. v3 only: TL_NO_PREFILL_V3
+// does not apply.
+py::object prefill_attn_carry(Tensor q, Tensor k, Tensor v, Tensor o_state,
+                              Tensor ml_state, double scale, bool causal,
+                              int64_t q_off, bool first, bool last,
+                              bool want_lse) {
+  CHECK_IN(q, torch::kBFloat16);
+  TORCH_CHECK(q.dim() == 4, "q must be [B,Sq,Hq,D]");
+  auto kv = prefill_kv(k, v, /*v3_only=*/true);
+  const int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
+  const int Skv = k.size(1);
+  const int Hkv = k.size(2);
+  TORCH_CHECK(D == 64 || D == 128, "head_dim must be 64 or 128");
+  TORCH_CHECK(k.size(0) == B && k.size(3) == D && Hq % Hkv == 0,
+              "k/v do not match q");
+  TORCH_CHECK(Sq >= 1 && Skv >= 1, "empty q or k/v chunk");
+  TORCH_CHECK(q_off >= 0 && (q_off + Sq <= Skv || !causal),
+              "q_off + Sq must fit Skv");
+  CHECK_IN(o_state, torch::kFloat);
+  CHECK_IN(ml_state, torch::kFloat);
+  TORCH_CHECK(o_state.get_device() == q.get_device() &&
+                  ml_state.get_device() == q.get_device(),
+              "state must be on q's device");
+  TORCH_CHECK(o_state.sizes() == q.sizes(), "o_state must be [B,Sq,Hq,D]");
+  TORCH_CHECK(ml_state.dim() == 4 && ml_state.size(0) == B &&
+                  ml_state.size(1) == Hq && ml_state.size(2) == Sq &&
+                  ml_state.size(3) == 2,
+              "ml_state must be [B,Hq,Sq,2]");
+  Tensor out, lse;
+  if (last) {
+    out = torch::empty_like(q);
+    if (want_lse)
+      lse = torch::empty({B, Hq, Sq}, q.options().dtype(torch::kFloat));
+  }
+  tl_prefill_attn_carry(
+      q.data_ptr(), kv.k.data_ptr(), kv.v.data_ptr(),
+      last ? out.data_ptr() : nullptr, lse.defined() ? lse.data_ptr() : nullptr,
+      o_state.data_ptr(), ml_state.data_ptr(), B, Sq, Skv, (int)q_off, Hq,
+      Hkv, D, (float)scale, causal ? 1 : 0, first ? 1 : 0, last ? 1 : 0,
+      kv.ks[0], kv.ks[1], kv.ks[2], kv.vs[0], kv.vs[1], kv.vs[2],
+      cur_stream());
+  if (!last) return py::none();
+  if (want_lse) return py::make_tuple(out, lse);
+  return py::cast(out);
 }
 
 std::vector<Tensor> attn_bwd(Tensor q, Tensor k, Tensor v, Tensor dout,
@@ -1011,6 +1068,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "split-K count of mxfp4_moe_gemm for (N, K, E)");
   mod.def("prefill_attn_lse", &prefill_attn_lse,
           "causal GQA prefill attention returning (out, logsumexp)");
+  mod.def("prefill_attn_carry", &prefill_attn_carry,
+          "prefill attention over one key chunk with carried (o, m, l) state",
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o_state"),
+          py::arg("ml_state"), py::arg("scale"), py::arg("causal"),
+          py::arg("q_off"), py::arg("first"), py::arg("last"),
+          py::arg("want_lse") = false);
   mod.def("attn_bwd", &attn_bwd,
           "flash-attention backward: (dq, dk, dv) from saved lse/delta");
 }

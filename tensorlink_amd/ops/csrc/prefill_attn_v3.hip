@@ -73,7 +73,7 @@ DEVINLINE void ds_read_tr16_frag4(unsigned addr_bytes, bf16x8_t (&f)[4]) {
 // expressions in v2's order. s = raw QK^T accumulators in, P written to
 // pw[16][BN + PPAD] as bf16. MASK = false only for tiles wholly below the
 // diagonal and below Skv, where v2's select always takes the product.
-template <bool MASK>
+template <bool MASK, bool PIN_FMA>
 DEVINLINE void softmax_frag(f32x4 (&s)[4], float (&m_run)[4],
                             float (&l_run)[4], float (&alpha)[4], int kt0,
                             int qrow0, int Skv, int causal, float scale,
@@ -128,20 +128,44 @@ DEVINLINE void softmax_frag(f32x4 (&s)[4], float (&m_run)[4],
     for (int r = 0; r < 4; ++r)
       psum[r] += __shfl_xor(psum[r], off, WAVE_SIZE);
 #pragma unroll
-  for (int r = 0; r < 4; ++r)
-    l_run[r] = l_run[r] * alpha[r] + psum[r];
+  for (int r = 0; r < 4; ++r) {
+    // the plain kernel's compile contracts this to one fma (as v2's does);
+    // the carried variant's does so for some rows only, so there the fma
+    // is spelled out. Spelling it out for both moves the plain kernel's
+    // register allocation, which stays as it was measured.
+    if constexpr (PIN_FMA)
+      l_run[r] = __builtin_fmaf(l_run[r], alpha[r], psum[r]);
+    else
+      l_run[r] = l_run[r] * alpha[r] + psum[r];
+  }
 }
 
 // Sq, Skv, q_off as in v2. k_s* / v_s* = batch, head and token strides in
 // elements of the [B,Skv,Hkv,D] views (D contiguous).
-template <int D>
+//
+// CARRY = 1 is the carried-state variant: the online-softmax state of a row
+// (m_run, l_run and the unnormalised oacc, all f32) starts from the caller's
+// buffers unless `first` and goes back to them unless `last`, so a sequence
+// of calls over key chunks is one softmax over their concatenation.
+//   o_state  [B,Sq,Hq,D]  unnormalised accumulator, indexed like out
+//   ml_state [B,Hq,Sq,2]  (m, l) per row as one 8-byte pair
+// The state is updated in place: a row's state is read in the prologue and
+// written in the epilogue by the same lanes of the same workgroup, and no
+// other workgroup touches that row, so there is no cross-workgroup hazard.
+// Rows past Sq keep the init values and touch no address. The tile loop
+// between prologue and epilogue is the same code for both variants; with
+// chunk boundaries on multiples of BN and chunks in ascending order the
+// carried calls run v3's tile steps in v3's order (bit-identical result).
+// CARRY = 0 ignores the four trailing arguments.
+template <int D, int CARRY>
 __global__ __launch_bounds__(BLOCK)
 __attribute__((amdgpu_waves_per_eu(2))) void prefill_attn_v3_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k,
     const bf16* __restrict__ v, bf16* __restrict__ out,
     float* __restrict__ lse, int B, int Sq, int Skv, int q_off, int Hq,
     int Hkv, float scale, int causal, int64_t k_sb, int64_t k_sh,
-    int64_t k_ss, int64_t v_sb, int64_t v_sh, int64_t v_ss) {
+    int64_t k_ss, int64_t v_sb, int64_t v_sh, int64_t v_ss, float* o_state,
+    float* ml_state, int first, int last) {
   static_assert(D == 64 || D == 128);
   constexpr int KCH = D / 32;      // QK^T k-chunks
   constexpr int NSUB = BN / 16;    // score col tiles = 4
@@ -189,6 +213,30 @@ __attribute__((amdgpu_waves_per_eu(2))) void prefill_attn_v3_kernel(
     for (int r = 0; r < 4; ++r) { m_run[f][r] = -1e30f; l_run[f][r] = 0.f; }
 #pragma unroll
     for (int n = 0; n < NS_PV; ++n) oacc[f][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  // C-fragment addressing of the state: 16 lanes cover 64 contiguous bytes
+  // of an o_state row; the 16 lanes of a quad share a row's (m, l) pair
+  if constexpr (CARRY) {
+    if (!first) {
+      const int64_t obase = ((int64_t)b * Sq) * Hq * D + (int64_t)h * D;
+      const int64_t mlbase = ((int64_t)b * Hq + h) * Sq;
+#pragma unroll
+      for (int f = 0; f < 2; ++f)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int qrow = q0 + r0 + f * 16 + quad * 4 + r;
+          if (qrow < Sq) {
+            const float2 ml = *reinterpret_cast<const float2*>(
+                ml_state + (mlbase + qrow) * 2);
+            m_run[f][r] = ml.x;
+            l_run[f][r] = ml.y;
+#pragma unroll
+            for (int n = 0; n < NS_PV; ++n)
+              oacc[f][n][r] =
+                  o_state[obase + (int64_t)qrow * Hq * D + n * 16 + col];
+          }
+        }
+    }
   }
 
   // key tiles: the block stages what its last live 64-row half needs; a
@@ -279,13 +327,15 @@ __attribute__((amdgpu_waves_per_eu(2))) void prefill_attn_v3_kernel(
 #pragma unroll
       for (int f = 0; f < 2; ++f) {
         if (need_mask)
-          softmax_frag<true>(sacc[f], m_run[f], l_run[f], alpha[f], kt0,
-                             q_off + q0 + r0 + f * 16, Skv, causal, scale,
-                             p_lds[wave], col, quad);
+          softmax_frag<true, CARRY != 0>(
+              sacc[f], m_run[f], l_run[f], alpha[f], kt0,
+              q_off + q0 + r0 + f * 16, Skv, causal, scale, p_lds[wave], col,
+              quad);
         else
-          softmax_frag<false>(sacc[f], m_run[f], l_run[f], alpha[f], kt0,
-                              q_off + q0 + r0 + f * 16, Skv, causal, scale,
-                              p_lds[wave], col, quad);
+          softmax_frag<false, CARRY != 0>(
+              sacc[f], m_run[f], l_run[f], alpha[f], kt0,
+              q_off + q0 + r0 + f * 16, Skv, causal, scale, p_lds[wave], col,
+              quad);
 #pragma unroll
         for (int ks = 0; ks < BN / 32; ++ks)
           pa[f][ks] = *reinterpret_cast<const bf16x8_t*>(
@@ -322,6 +372,30 @@ __attribute__((amdgpu_waves_per_eu(2))) void prefill_attn_v3_kernel(
     __syncthreads();   // tile t+1 visible; tile t's buffer free for t+2
   }
 
+  // ---- carried epilogue: the state goes back as it is, out untouched ----
+  if constexpr (CARRY) {
+    if (!last) {
+      const int64_t obase = ((int64_t)b * Sq) * Hq * D + (int64_t)h * D;
+      const int64_t mlbase = ((int64_t)b * Hq + h) * Sq;
+#pragma unroll
+      for (int f = 0; f < 2; ++f)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int qrow = q0 + r0 + f * 16 + quad * 4 + r;
+          if (qrow < Sq) {
+#pragma unroll
+            for (int n = 0; n < NS_PV; ++n)
+              o_state[obase + (int64_t)qrow * Hq * D + n * 16 + col] =
+                  oacc[f][n][r];
+            if (col == 0)
+              *reinterpret_cast<float2*>(ml_state + (mlbase + qrow) * 2) =
+                  make_float2(m_run[f][r], l_run[f][r]);
+          }
+        }
+      return;
+    }
+  }
+
   // ---- epilogue: divide by l, store (+ logsumexp for backward) ----
   {
     const int64_t obase = ((int64_t)b * Sq) * Hq * D + (int64_t)h * D;
@@ -354,13 +428,41 @@ extern "C" void tl_prefill_attn_v3(
     int64_t v_sh, int64_t v_ss, hipStream_t stream) {
   dim3 grid((Sq + BM - 1) / BM, Hq, B), block(BLOCK);
   if (D == 128)
-    hipLaunchKernelGGL((prefill_attn_v3_kernel<128>), grid, block, 0, stream,
-                       (const bf16*)q, (const bf16*)k, (const bf16*)v,
-                       (bf16*)out, (float*)lse, B, Sq, Skv, q_off, Hq, Hkv,
-                       scale, causal, k_sb, k_sh, k_ss, v_sb, v_sh, v_ss);
+    hipLaunchKernelGGL((prefill_attn_v3_kernel<128, 0>), grid, block, 0,
+                       stream, (const bf16*)q, (const bf16*)k,
+                       (const bf16*)v, (bf16*)out, (float*)lse, B, Sq, Skv,
+                       q_off, Hq, Hkv, scale, causal, k_sb, k_sh, k_ss, v_sb,
+                       v_sh, v_ss, (float*)nullptr, (float*)nullptr, 1, 1);
   else if (D == 64)
-    hipLaunchKernelGGL((prefill_attn_v3_kernel<64>), grid, block, 0, stream,
-                       (const bf16*)q, (const bf16*)k, (const bf16*)v,
-                       (bf16*)out, (float*)lse, B, Sq, Skv, q_off, Hq, Hkv,
-                       scale, causal, k_sb, k_sh, k_ss, v_sb, v_sh, v_ss);
+    hipLaunchKernelGGL((prefill_attn_v3_kernel<64, 0>), grid, block, 0,
+                       stream, (const bf16*)q, (const bf16*)k,
+                       (const bf16*)v, (bf16*)out, (float*)lse, B, Sq, Skv,
+                       q_off, Hq, Hkv, scale, causal, k_sb, k_sh, k_ss, v_sb,
+                       v_sh, v_ss, (float*)nullptr, (float*)nullptr, 1, 1);
+}
+
+// Carried-state entry: one key chunk of a longer softmax per call (see the
+// kernel's comment). out / lse are written only when `last` (lse may be
+// null); the state is read unless `first` and written unless `last`.
+extern "C" void tl_prefill_attn_carry(
+    const void* q, const void* k, const void* v, void* out, void* lse,
+    void* o_state, void* ml_state, int B, int Sq, int Skv, int q_off, int Hq,
+    int Hkv, int D, float scale, int causal, int first, int last,
+    int64_t k_sb, int64_t k_sh, int64_t k_ss, int64_t v_sb, int64_t v_sh,
+    int64_t v_ss, hipStream_t stream) {
+  dim3 grid((Sq + BM - 1) / BM, Hq, B), block(BLOCK);
+  if (D == 128)
+    hipLaunchKernelGGL((prefill_attn_v3_kernel<128, 1>), grid, block, 0,
+                       stream, (const bf16*)q, (const bf16*)k,
+                       (const bf16*)v, (bf16*)out, (float*)lse, B, Sq, Skv,
+                       q_off, Hq, Hkv, scale, causal, k_sb, k_sh, k_ss, v_sb,
+                       v_sh, v_ss, (float*)o_state, (float*)ml_state, first,
+                       last);
+  else if (D == 64)
+    hipLaunchKernelGGL((prefill_attn_v3_kernel<64, 1>), grid, block, 0,
+                       stream, (const bf16*)q, (const bf16*)k,
+                       (const bf16*)v, (bf16*)out, (float*)lse, B, Sq, Skv,
+                       q_off, Hq, Hkv, scale, causal, k_sb, k_sh, k_ss, v_sb,
+                       v_sh, v_ss, (float*)o_state, (float*)ml_state, first,
+                       last);
 }

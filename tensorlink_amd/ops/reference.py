@@ -114,6 +114,56 @@ def attention_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     return out.transpose(1, 2).to(q.dtype)
 
 
+def attention_prefill_carry(q: torch.Tensor, k: torch.Tensor,
+                            v: torch.Tensor, o_state: torch.Tensor,
+                            ml_state: torch.Tensor, causal: bool = True,
+                            scale: Optional[float] = None, q_off: int = 0,
+                            first: bool = True, last: bool = True):
+    """One key chunk of an online softmax whose state the caller carries
+    between calls. q [B,Sq,Hq,D], k/v [B,Skv,Hkv,D] (this chunk only; with
+    causal, key j is visible to row i when j <= q_off + i).
+
+    o_state [B,Sq,Hq,D] fp32 is the UNNORMALISED accumulator and ml_state
+    [B,Hq,Sq,2] fp32 the (running max, running sum) per row; a row that has
+    seen no key holds (-1e30, 0) and a zero accumulator. The state is not
+    read when ``first`` and is updated in place unless ``last``; ``last``
+    returns o / l in q's dtype instead (0 for a row with no key) and leaves
+    the state alone. Returns None when not ``last``."""
+    B, Sq, Hq, D = q.shape
+    Skv, Hkv = k.shape[1], k.shape[2]
+    scale = scale or 1.0 / math.sqrt(D)
+    rep = Hq // Hkv
+    qf = q.float().transpose(1, 2)                       # [B,Hq,Sq,D]
+    kf = k.float().transpose(1, 2).repeat_interleave(rep, dim=1)
+    vf = v.float().transpose(1, 2).repeat_interleave(rep, dim=1)
+    scores = torch.matmul(qf, kf.transpose(-1, -2)) * scale
+    if causal:
+        rows = torch.arange(Sq, device=q.device).unsqueeze(1) + q_off
+        cols = torch.arange(Skv, device=q.device).unsqueeze(0)
+        scores = scores.masked_fill(cols > rows, float("-inf"))
+    if first:
+        m_prev = torch.full((B, Hq, Sq), -1e30, dtype=torch.float32,
+                            device=q.device)
+        l_prev = torch.zeros_like(m_prev)
+        o_prev = torch.zeros(B, Hq, Sq, D, dtype=torch.float32,
+                             device=q.device)
+    else:
+        m_prev, l_prev = ml_state[..., 0], ml_state[..., 1]
+        o_prev = o_state.transpose(1, 2)
+    m_new = torch.maximum(m_prev, scores.amax(-1))       # >= -1e30
+    p = torch.exp(scores - m_new.unsqueeze(-1))          # masked -> 0
+    alpha = torch.exp(m_prev - m_new)
+    l_new = l_prev * alpha + p.sum(-1)
+    o_new = o_prev * alpha.unsqueeze(-1) + torch.matmul(p, vf)
+    if last:
+        linv = torch.where(l_new > 0, 1.0 / l_new, torch.zeros_like(l_new))
+        return (o_new * linv.unsqueeze(-1)).transpose(1, 2).to(q.dtype)
+    o_state.copy_(o_new.transpose(1, 2))
+    ml_state[..., 0] = m_new
+    ml_state[..., 1] = l_new
+    return None
+
+
 def attention_decode(q: torch.Tensor, k_cache: torch.Tensor,
                      v_cache: torch.Tensor, seq_lens: torch.Tensor,
                      scale: Optional[float] = None) -> torch.Tensor:

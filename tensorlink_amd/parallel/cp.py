@@ -16,13 +16,18 @@ every step merges the per-rank partial attentions with one all-gather of
 online-softmax partials/merge are plain differentiable torch math with
 the row max detached (softmax is shift-invariant, so detaching is
 exact), and per-chunk losses + an all-reduce grad sum reproduce the
-full-sequence gradient. The kernel-grade version would fuse the merge
-into prefill_attn.hip.
+full-sequence gradient. On the GPU the prefill ring runs on the MFMA
+prefill kernel: each contributing ring step is one carried-state call
+(ops.attention_prefill_carry) that merges the chunk into a per-rank fp32
+(o, m, l) state in place, so no score tensor exists (TL_NO_CP_KERNEL=1
+restores the torch math). CP decode and CPTrainer still run the torch
+math.
 """
 
 from __future__ import annotations
 
 import math
+import os
 from typing import Optional
 
 import torch
@@ -75,6 +80,44 @@ def _merge(acc, nxt):
     return o, m, l
 
 
+def _ring_accumulate(q, scale, rank, steps):
+    """Attention of this rank's queries q [B,Sq,H,D] over the K/V chunks a
+    ring hands it. ``steps`` yields (src_chunk, k, v) with the rank's own
+    (diagonal) chunk first; chunks with src_chunk > rank lie in the future
+    and are skipped, but the iterator is always drained (the ring rotates
+    between its items). Returns the normalised [B,Sq,H,D] output.
+
+    GPU bf16 at head dim 64 / 128: one carried-state kernel call per
+    contributing chunk, the state merged in place and the call on chunk 0
+    (the last contributing one in ring order) writing the bf16 output.
+    TL_NO_CP_KERNEL=1 (read per call) and everything else: the torch-math
+    partials and merge, output in fp32."""
+    off = os.environ.get("TL_NO_CP_KERNEL", "")
+    if (q.is_cuda and q.dtype == torch.bfloat16 and q.shape[-1] in (64, 128)
+            and off in ("", "0")):
+        carry = ops.AttnCarry.empty(q)
+        out, started = None, False
+        for src_chunk, k, v in steps:
+            if src_chunk > rank:
+                continue
+            diag = src_chunk == rank
+            assert diag != started, "the diagonal chunk comes first"
+            started = True
+            res = ops.attention_prefill_carry(
+                q, k, v, carry, causal=diag, q_off=0, scale=scale,
+                first=diag, last=src_chunk == 0)
+            if res is not None:
+                out = res
+        return out
+    acc = None
+    for src_chunk, k, v in steps:
+        if src_chunk <= rank:
+            acc = _merge(acc, _partial_attn(q, k, v, scale,
+                                            causal_diag=src_chunk == rank))
+    o, m, l = acc
+    return o / l.permute(0, 2, 1).unsqueeze(-1).clamp(min=1e-30)
+
+
 class CPRunner:
     """Sequence-sharded prefill across a CP group (weights replicated,
     same seeded init on every rank)."""
@@ -116,18 +159,16 @@ class CPRunner:
         if layer_idx is not None:
             self._kv[layer_idx] = (k.clone(), v.clone())
 
-        acc = None
+        out = _ring_accumulate(q, scale, self.rank, self._ring_steps(k, v))
+        return attn.o_proj(out.to(x.dtype).reshape(B, Sq, -1))
+
+    def _ring_steps(self, k, v):
+        """The ring as seen from this rank: yields (src_chunk, k, v) for
+        each of the cp steps and rotates K/V to the next rank between
+        them."""
         cur_k, cur_v = k, v
         for r in range(self.cp):
-            src_chunk = (self.rank - r) % self.cp
-            if src_chunk == self.rank:
-                part = _partial_attn(q, cur_k, cur_v, scale,
-                                     causal_diag=True)
-                acc = _merge(acc, part)
-            elif src_chunk < self.rank:
-                part = _partial_attn(q, cur_k, cur_v, scale,
-                                     causal_diag=False)
-                acc = _merge(acc, part)
+            yield (self.rank - r) % self.cp, cur_k, cur_v
             # rotate K/V to the next rank (skip after the last step)
             if r < self.cp - 1 and self.cp > 1:
                 nk = torch.empty_like(cur_k)
@@ -141,9 +182,6 @@ class CPRunner:
                 for w in reqs:
                     w.wait()
                 cur_k, cur_v = nk, nv
-        o, m, l = acc
-        out = (o / l.permute(0, 2, 1).unsqueeze(-1).clamp(min=1e-30))
-        return attn.o_proj(out.to(x.dtype).reshape(B, Sq, -1))
 
     @torch.no_grad()
     def forward_logits(self, input_ids: torch.Tensor,
