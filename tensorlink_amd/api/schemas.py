@@ -19,7 +19,8 @@ class JobRequest(BaseModel):
     max_ctx: int = 4096
     prefill_chunk: Optional[int] = None
     prefix_caching: bool = False
-    quantize: Optional[str] = None    # fp8 | fp8-dense | fp4 | fp4-dense
+    # fp8 | fp8-dense | fp4 | fp4-dense | fp4-dense-a8
+    quantize: Optional[str] = None
 
 
 class GenerationRequest(BaseModel):

@@ -201,25 +201,33 @@ class Fp4Linear(nn.Module):
     goes through ops.mxfp4_linear: on GPU the packed weights feed the
     hand-written GEMM (ops/csrc/mxfp4_gemm.hip, hipGraph-capturable, no
     dequantized copy is kept); on CPU the fp32 reference dequantizes per
-    call. The scaled-MFMA variant for compute-bound M is open work
-    (ROADMAP.md §6)."""
+    call. ``act_quant="mxfp8"`` (opt-in: it changes what the layer
+    computes) also quantizes the activations, per row and 32-group, and
+    from ops.MXFP4_A8_M_MIN rows on the same packed weights feed the
+    scaled-MFMA GEMM (ops/csrc/mxfp4_a8_gemm.hip) for compute-bound M:
+    prefill, chunked prefill, large decode batches. Smaller calls keep the
+    weight-only kernel."""
 
-    def __init__(self, packed, exponents, bias, in_features, out_features):
+    def __init__(self, packed, exponents, bias, in_features, out_features,
+                 act_quant=None):
         super().__init__()
         self.register_buffer("packed", packed)
         self.register_buffer("exponents", exponents)
         self.bias = bias
         self.in_features = in_features
         self.out_features = out_features
+        self.act_quant = act_quant
 
     @classmethod
-    def from_linear(cls, lin: nn.Linear) -> "Fp4Linear":
+    def from_linear(cls, lin: nn.Linear, act_quant=None) -> "Fp4Linear":
         packed, e = quantize_mxfp4_rows(lin.weight.detach())
-        return cls(packed, e, lin.bias, lin.in_features, lin.out_features)
+        return cls(packed, e, lin.bias, lin.in_features, lin.out_features,
+                   act_quant)
 
     def forward(self, x):
         from tensorlink_amd import ops
-        return ops.mxfp4_linear(x, self.packed, self.exponents, self.bias)
+        return ops.mxfp4_linear(x, self.packed, self.exponents, self.bias,
+                                act_quant=self.act_quant)
 
 
 def quantize_experts_fp4(stage: nn.Module) -> int:
@@ -242,11 +250,12 @@ def quantize_experts_fp4(stage: nn.Module) -> int:
     return n
 
 
-def quantize_dense_fp4(stage: nn.Module) -> int:
+def quantize_dense_fp4(stage: nn.Module, act_quant=None) -> int:
     """Convert every projection Linear to weight-only MXFP4 in place
     (4-bit analog of quantize_dense_fp8). On an MoE model this covers the
     expert projections too, which then take the grouped kernel like
-    quantize_experts_fp4's."""
+    quantize_experts_fp4's. ``act_quant`` is handed to every Fp4Linear;
+    the grouped expert path ignores it (experts stay weight-only)."""
     n = 0
     targets = ("qkv_proj", "o_proj", "gate_up_proj", "down_proj")
     for mod in stage.modules():
@@ -254,6 +263,6 @@ def quantize_dense_fp4(stage: nn.Module) -> int:
             lin = getattr(mod, name, None)
             if isinstance(lin, nn.Linear) and not isinstance(
                     lin, (Fp8Linear,)):
-                setattr(mod, name, Fp4Linear.from_linear(lin))
+                setattr(mod, name, Fp4Linear.from_linear(lin, act_quant))
                 n += 1
     return n

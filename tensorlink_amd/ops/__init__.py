@@ -676,22 +676,73 @@ def _use_mxfp4_gemm(M: int, N: int, K: int) -> bool:
             and 1 <= M <= min(GEMM_M_MAX, 512))
 
 
+# MXFP4 x MXFP8 path (ops/csrc/mxfp4_a8_gemm.hip): incremented whenever the
+# quantizer + scaled-MFMA GEMM pair handles a linear
+mxfp4_a8_dispatch_count = 0
+
+# smallest M at which act_quant="mxfp8" leaves the weight-only kernel for the
+# quantizer + scaled-MFMA GEMM. Measured (profiles/mxfp4_a8_gemm.md): the
+# first benchmarked M from which the pair beats today's route on all four
+# Qwen2.5-7B projections; at 256 the deep-K down projection still loses.
+# Tests set the attribute; TL_MXFP4_A8_M_MIN overrides it at import.
+MXFP4_A8_M_MIN = int(_os.environ.get("TL_MXFP4_A8_M_MIN", "512"))
+
+
+def _use_mxfp4_a8(M: int, N: int, K: int) -> bool:
+    return (N > 0 and N % 64 == 0 and K > 0 and K % 128 == 0
+            and M >= max(1, MXFP4_A8_M_MIN))
+
+
+def quantize_mxfp8(x: torch.Tensor):
+    """MXFP8 activation quantizer: x [.., K] -> (codes [.., K] uint8 e4m3,
+    scales [.., K/32] uint8 e8m0), the bytes of
+    ops.reference.quantize_mxfp8. GPU bf16 input with K % 128 == 0 runs the
+    HIP kernel (one pass, no host sync); everything else the reference."""
+    if (_on_gpu(x) and x.dtype == torch.bfloat16 and x.numel() > 0
+            and x.shape[-1] % 128 == 0):
+        codes, scales = _require_ext().mx_quant_act(x.contiguous())
+        return codes, scales
+    return ref.quantize_mxfp8(x)
+
+
 def mxfp4_linear(x: torch.Tensor, packed: torch.Tensor,
                  exponents: torch.Tensor,
-                 bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 bias: Optional[torch.Tensor] = None,
+                 act_quant: Optional[str] = None) -> torch.Tensor:
     """x @ dequant(packed, exponents)^T + bias for MXFP4 weights as
     models.quant.quantize_mxfp4 emits them (packed [N, K/2] uint8,
     exponents [N, K/32] int8). GPU bf16 rows at serving M run the
     hand-written weight-only kernel (ops/csrc/mxfp4_gemm.hip): bitwise
     M-independent rows, hipGraph-capturable, no dequantized copy. Other
     GPU inputs dequantize once to bf16 (exact) and use F.linear; CPU runs
-    the fp32 reference."""
-    global mxfp4_dispatch_count
+    the fp32 reference.
+
+    act_quant="mxfp8" (opt-in; it changes what is computed) quantizes the
+    activations to MXFP8 (ops.reference.quantize_mxfp8) and, on GPU bf16
+    rows with M >= MXFP4_A8_M_MIN in a supported shape (N % 64 == 0,
+    K % 128 == 0, any M), runs quantizer + scaled-MFMA GEMM
+    (ops/csrc/mxfp4_a8_gemm.hip): no split-K, a row's bits depend on that
+    row and the weights alone. Below the threshold and in unsupported
+    shapes the call behaves as with act_quant=None; on CPU it is
+    reference.mxfp4_a8_linear at every M."""
+    global mxfp4_dispatch_count, mxfp4_a8_dispatch_count
+    if act_quant not in (None, "mxfp8"):
+        raise ValueError(f"unknown act_quant {act_quant!r}")
     if not _on_gpu(x):
+        if act_quant == "mxfp8":
+            return ref.mxfp4_a8_linear(x, packed, exponents, bias)
         return ref.mxfp4_linear(x, packed, exponents, bias)
     K = x.shape[-1]
     M = x.numel() // K if K else 0
     N = packed.shape[0]
+    if (act_quant == "mxfp8" and x.dtype == torch.bfloat16
+            and _C is not None and _use_mxfp4_a8(M, N, K)):
+        mxfp4_a8_dispatch_count += 1
+        xq, xs = _C.mx_quant_act(x.contiguous())
+        return _C.mxfp4_a8_gemm(
+            xq, xs, packed.contiguous(), exponents.contiguous(),
+            bias.to(torch.bfloat16).contiguous()
+            if bias is not None else None)
     if (x.dtype == torch.bfloat16 and _C is not None
             and _use_mxfp4_gemm(M, N, K)):
         mxfp4_dispatch_count += 1

@@ -82,6 +82,12 @@ void tl_moe_gemm(const void* x, const void* tok_idx, const void* seg_off,
 void tl_mxfp4_gemm(const void* x, const void* packed, const void* exps,
                    const void* bias, void* out, void* partial, int M, int N,
                    int K, int n_split, hipStream_t stream);
+int tl_mxfp4_a8_tile(int M, int N);
+void tl_mxfp4_a8_gemm(const void* xq, const void* xs, const void* packed,
+                      const void* exps, const void* bias, void* out, int M,
+                      int N, int K, int tile, hipStream_t stream);
+void tl_mx_quant_act(const void* x, void* codes, void* scales,
+                     int64_t n_elems, hipStream_t stream);
 void tl_mxfp4_moe_gemm(const void* x, const void* tok_idx,
                        const void* seg_off, const void* p_ptrs,
                        const void* e_ptrs, void* out, void* partial, int T,
@@ -875,6 +881,79 @@ Tensor mxfp4_gemm(Tensor x, Tensor packed, Tensor exponents,
   return out;
 }
 
+// MXFP8 activation quantizer (mxfp4_a8_gemm.hip): x bf16 [.., K] ->
+// (codes [.., K] uint8 e4m3, scales [.., K/32] uint8 e8m0), the bytes of
+// ops.reference.quantize_mxfp8. No host sync; allocates only its outputs.
+std::vector<Tensor> mx_quant_act(Tensor x) {
+  CHECK_IN(x, torch::kBFloat16);
+  TORCH_CHECK(x.dim() >= 1, "x must have a K dimension");
+  const int64_t K = x.size(-1);
+  TORCH_CHECK(K > 0 && K % 128 == 0 && x.numel() > 0,
+              "unsupported shape: need K % 128 == 0 and at least one row");
+  auto opts = x.options().dtype(torch::kByte);
+  auto codes = torch::empty(x.sizes(), opts);
+  auto ssz = x.sizes().vec();
+  ssz.back() = K / 32;
+  auto scales = torch::empty(ssz, opts);
+  tl_mx_quant_act(x.data_ptr(), codes.data_ptr(), scales.data_ptr(),
+                  x.numel(), cur_stream());
+  return {codes, scales};
+}
+
+int64_t mxfp4_a8_tile_py(int64_t M, int64_t N) {
+  TORCH_CHECK(M >= 1 && N > 0 && N % 64 == 0 && M < (1LL << 31) &&
+                  N < (1LL << 31),
+              "unsupported shape");
+  return tl_mxfp4_a8_tile((int)M, (int)N);
+}
+
+// MXFP4 x MXFP8 GEMM on the scaled MFMA (mxfp4_a8_gemm.hip). tile: 0 = the
+// shape's own choice (mxfp4_a8_tile), 128 / 256 force an instantiation
+// (tests: a row's bits do not depend on it).
+Tensor mxfp4_a8_gemm(Tensor xq, Tensor xs, Tensor packed, Tensor exponents,
+                     c10::optional<Tensor> bias, int64_t tile) {
+  CHECK_IN(xq, torch::kByte);
+  CHECK_IN(xs, torch::kByte);
+  CHECK_IN(packed, torch::kByte);
+  CHECK_IN(exponents, torch::kChar);
+  TORCH_CHECK(packed.dim() == 2 && exponents.dim() == 2,
+              "packed / exponents must be 2-D");
+  TORCH_CHECK(xq.dim() >= 1 && xs.dim() == xq.dim(),
+              "xq / xs must have a K dimension");
+  TORCH_CHECK(tile == 0 || tile == 128 || tile == 256,
+              "tile must be 0, 128 or 256");
+  const int64_t K = xq.size(-1);
+  const int64_t N = packed.size(0);
+  TORCH_CHECK(K > 0 && N > 0 && N % 64 == 0 && K % 128 == 0,
+              "unsupported shape: need N % 64 == 0 and K % 128 == 0");
+  TORCH_CHECK(packed.size(1) * 2 == K, "packed must be [N, K/2]");
+  TORCH_CHECK(exponents.size(0) == N && exponents.size(1) * 32 == K,
+              "exponents must be [N, K/32]");
+  const int64_t M = xq.numel() / K;
+  TORCH_CHECK(M >= 1 && M < (1LL << 31) && N < (1LL << 31) &&
+                  K < (1LL << 31),
+              "mxfp4_a8_gemm: call too large");
+  TORCH_CHECK(xs.size(-1) * 32 == K && xs.numel() * 32 == xq.numel(),
+              "xs must be [.., K/32]");
+  TORCH_CHECK(xs.device() == xq.device() && packed.device() == xq.device() &&
+                  exponents.device() == xq.device(),
+              "operands must share a device");
+  auto sizes = xq.sizes().vec();
+  sizes.back() = N;
+  auto out = torch::empty(sizes, xq.options().dtype(torch::kBFloat16));
+  const void* bp = nullptr;
+  if (bias.has_value()) {
+    CHECK_IN(bias.value(), torch::kBFloat16);
+    TORCH_CHECK(bias->numel() == N && bias->device() == xq.device(),
+                "bias must be [N] on the operands' device");
+    bp = bias->data_ptr();
+  }
+  tl_mxfp4_a8_gemm(xq.data_ptr(), xs.data_ptr(), packed.data_ptr(),
+                   exponents.data_ptr(), bp, out.data_ptr(), (int)M, (int)N,
+                   (int)K, (int)tile, cur_stream());
+  return out;
+}
+
 Tensor sample_tokens(Tensor logits, Tensor temps, Tensor top_ps,
                      Tensor top_ks, Tensor pres, Tensor freqs,
                      c10::optional<Tensor> counts,
@@ -1058,6 +1137,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "weight-only MXFP4 GEMM: x @ dequant(packed, exponents)^T + bias");
   mod.def("mxfp4_n_split", &mxfp4_n_split_py,
           "split-K count of mxfp4_gemm for (N, K)");
+  mod.def("mx_quant_act", &mx_quant_act,
+          "MXFP8 activation quantizer: bf16 -> (e4m3 codes, e8m0 scales)");
+  mod.def("mxfp4_a8_gemm", &mxfp4_a8_gemm,
+          "MXFP4 x MXFP8 GEMM on the scaled MFMA",
+          pybind11::arg("xq"), pybind11::arg("xs"), pybind11::arg("packed"),
+          pybind11::arg("exponents"), pybind11::arg("bias"),
+          pybind11::arg("tile") = 0);
+  mod.def("mxfp4_a8_tile", &mxfp4_a8_tile_py,
+          "tile edge (128 or 256) mxfp4_a8_gemm picks for (M, N)");
   mod.def("mxfp4_moe_gemm", &mxfp4_moe_gemm,
           "grouped MXFP4 expert GEMM over expert-sorted pair rows",
           pybind11::arg("x"), pybind11::arg("tok_idx"),

@@ -394,3 +394,60 @@ def mxfp4_moe_grouped(x: torch.Tensor, tok_idx: Optional[torch.Tensor],
         w = dequantize_mxfp4(packed[e], exponents[e], dtype=torch.float32)
         out[a:b] = rows.float() @ w.t()
     return out.to(x.dtype)
+
+
+# --------------------------------------------------------------------------
+# MXFP8 (OCP microscaling fp8, e4m3) activations for the MXFP4 x MXFP8 GEMM
+# --------------------------------------------------------------------------
+MXFP8_GROUP = 32
+_E4M3_MAX = 448.0
+
+
+def quantize_mxfp8(x: torch.Tensor):
+    """x [.., K] (K % 32 == 0, finite) -> (codes [.., K] uint8 holding
+    e4m3 bit patterns, scales [.., K/32] uint8 e8m0). Per 32-group:
+    scale byte s = clamp(biased_exponent(amax) - 8, 0, 254), i.e.
+    floor(log2 amax) - emax(e4m3) biased by 127 (0 for an all-zero group);
+    elements x / 2^(s-127), clamped to +-448 (the OCP rule saturates the
+    top of the binade), rounded to nearest even into e4m3. The contract of
+    ops.quantize_mxfp8 (ops/csrc/mxfp4_a8_gemm.hip), byte for byte."""
+    K = x.shape[-1]
+    assert K % MXFP8_GROUP == 0
+    xf = x.float().reshape(*x.shape[:-1], K // MXFP8_GROUP, MXFP8_GROUP)
+    amax = xf.abs().amax(-1)
+    biased = (amax.view(torch.int32) >> 23) & 0xFF
+    s = (biased - 8).clamp(0, 254)
+    # 2^(127-s), built from its exponent bits: exact on every device (a
+    # device pow need not be), in [2^-119, 2^127] for finite inputs
+    inv = ((254 - s).to(torch.int32) << 23).view(torch.float32)
+    y = (xf * inv.unsqueeze(-1)).clamp(-_E4M3_MAX, _E4M3_MAX)
+    # the cast itself runs on the CPU wherever x lives: it is the contract
+    # (ties to even), and a device's own fp8 cast need not round ties so
+    codes = y.cpu().to(torch.float8_e4m3fn).view(torch.uint8).to(x.device)
+    return codes.reshape(x.shape), s.to(torch.uint8)
+
+
+def dequantize_mxfp8(codes: torch.Tensor, scales: torch.Tensor,
+                     dtype=torch.float32):
+    """Inverse map of quantize_mxfp8: e4m3 value times 2^(scale - 127).
+    Exact in fp32 and fp64; bf16 holds it exactly wherever the product is
+    a normal bf16 (an e4m3 value has 4 significant bits)."""
+    wide = torch.float64 if dtype == torch.float64 else torch.float32
+    v = codes.view(torch.float8_e4m3fn).to(wide)
+    # 2^(scale-127) from its bits (byte 0 is the subnormal 2^-127)
+    sb = scales.to(torch.int32)
+    p2 = torch.where(sb > 0, sb << 23, torch.full_like(sb, 1 << 22))
+    p2 = p2.view(torch.float32).to(wide).repeat_interleave(MXFP8_GROUP, -1)
+    return (v * p2).to(dtype)
+
+
+def mxfp4_a8_linear(x: torch.Tensor, packed: torch.Tensor,
+                    exponents: torch.Tensor,
+                    bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mxfp4_linear on MXFP8-quantized activations: quantize, dequantize,
+    fp32 linear, cast to x.dtype. The contract of the quantizer + GEMM pair
+    in ops/csrc/mxfp4_a8_gemm.hip."""
+    xq = dequantize_mxfp8(*quantize_mxfp8(x), dtype=torch.float32)
+    w = dequantize_mxfp4(packed, exponents, dtype=torch.float32)
+    y = F.linear(xq, w, bias.float() if bias is not None else None)
+    return y.to(x.dtype)

@@ -128,10 +128,14 @@ class PipelineRunner:
             # extension every call dequantizes, so decode stays eager
             if not _ops.extension_loaded():
                 self._no_graph = True
-        elif quantize == "fp4-dense":
+        elif quantize in ("fp4-dense", "fp4-dense-a8"):
             from tensorlink_amd.models.quant import quantize_dense_fp4
             from tensorlink_amd import ops as _ops
-            quantize_dense_fp4(self.stage)
+            # -a8: MXFP8 activations from ops.MXFP4_A8_M_MIN rows on
+            # (mxfp4_a8_gemm.hip, capture-safe as well)
+            quantize_dense_fp4(
+                self.stage,
+                act_quant="mxfp8" if quantize == "fp4-dense-a8" else None)
             # same rule as fp8-dense: with the extension the projections
             # run mxfp4_gemm.hip (no host sync, capture-safe); only the
             # per-call dequant fallback keeps decode eager
