@@ -18,6 +18,7 @@ from __future__ import annotations
 import dataclasses
 
 import math
+import os
 from typing import List, Optional
 
 import torch
@@ -261,6 +262,8 @@ class MoEMLP(nn.Module):
     """Mixtral-style sparse MoE block (new capability — the reference has no
     MoE-aware code)."""
 
+    fused_router = False    # opt-in: see _use_fused_router
+
     def __init__(self, config: ModelConfig):
         super().__init__()
         h, i = config.hidden_size, config.intermediate_size
@@ -298,6 +301,18 @@ class MoEMLP(nn.Module):
             return "bf16"
         return None
 
+    def _use_fused_router(self, H):
+        """Opt-in (fused_router = True or TL_MOE_FUSED_ROUTER=1, read per
+        call): route through ops.moe_route (moe_route.hip) instead of
+        self.gate + the reference router. Only asked on the fused GPU
+        path. The logits leave the library GEMM, so a near-tie can pick
+        another expert than the default route does."""
+        return ((self.fused_router
+                 or os.environ.get("TL_MOE_FUSED_ROUTER") == "1")
+                and type(self.gate) is nn.Linear and self.gate.bias is None
+                and self.gate.weight.dtype == torch.bfloat16
+                and ops.moe_route_served(H, self.num_experts, self.top_k))
+
     def _tables(self, dev, kind):
         """Device pointer tables into the per-expert weights (no stacked
         copy); rebuilt if weights moved. The second pair holds what goes
@@ -333,9 +348,12 @@ class MoEMLP(nn.Module):
 
     def _fused_forward(self, flat, rw, idx, kind=None):
         """Grouped expert GEMMs over expert-sorted (token, slot) pairs;
-        deterministic combine: inverse-permutation gather then a fixed
-        slot-order sum (no atomics — batcher greedy equality holds for
-        MoE models too). hipGraph-capture-safe end to end."""
+        deterministic combine: each token's k weighted rows summed in
+        fp32 in slot order (no atomics — batcher greedy equality holds
+        for MoE models too). The dispatch plan and the combine are
+        ops/csrc/moe_route.hip wherever it serves the shapes;
+        TL_NO_MOE_PLAN=1 (read per call) keeps the torch glue they
+        replace. hipGraph-capture-safe end to end."""
         C = ops._require_ext()
         kind = kind if kind is not None else self._fused_kind()
         E, k = self.num_experts, self.top_k
@@ -343,15 +361,22 @@ class MoEMLP(nn.Module):
         P = T * k
         dev = flat.device
         gu_p, down_p, gu_s, down_s = self._tables(dev, kind)
-        fi = idx.reshape(-1)
-        order = fi.argsort(stable=True)
-        # counts via scatter_add (torch.bincount device-syncs, which
-        # breaks hipGraph capture of quantized-MoE decode)
-        counts = torch.zeros(E, device=dev, dtype=torch.long)
-        counts.scatter_add_(0, fi, torch.ones_like(fi))
-        seg = torch.zeros(E + 1, device=dev, dtype=torch.int32)
-        seg[1:] = counts.cumsum(0)
-        pair_tok = (order // k).to(torch.int32)
+        planned = (rw.dtype == torch.bfloat16
+                   and idx.dtype in (torch.int64, torch.int32)
+                   and ops.moe_plan_served(T, k, E, H)
+                   and os.environ.get("TL_NO_MOE_PLAN") != "1")
+        if planned:
+            seg, pair_tok, pos = ops.moe_plan(idx.reshape(T, k), E)
+        else:
+            fi = idx.reshape(-1).long()
+            order = fi.argsort(stable=True)
+            # counts via scatter_add (torch.bincount device-syncs, which
+            # breaks hipGraph capture of quantized-MoE decode)
+            counts = torch.zeros(E, device=dev, dtype=torch.long)
+            counts.scatter_add_(0, fi, torch.ones_like(fi))
+            seg = torch.zeros(E + 1, device=dev, dtype=torch.int32)
+            seg[1:] = counts.cumsum(0)
+            pair_tok = (order // k).to(torch.int32)
         Ie = self.experts[0].inter
         if kind == "fp4":
             gu = ops.mxfp4_moe_gemm(flat.contiguous(), pair_tok, seg, gu_p,
@@ -364,6 +389,8 @@ class MoEMLP(nn.Module):
                             2 * Ie, fp8)
             act = ops.swiglu_fused(gu)
             y_pairs = C.moe_gemm(act, None, seg, down_p, down_s, H, fp8)
+        if planned:
+            return ops.moe_combine(y_pairs, rw.reshape(T, k), pos)
         y_pairs = y_pairs * rw.reshape(-1)[order].unsqueeze(1)
         inv = torch.empty_like(order)
         inv[order] = torch.arange(P, device=dev, dtype=order.dtype)
@@ -372,14 +399,20 @@ class MoEMLP(nn.Module):
     def forward(self, x):
         B, S, H = x.shape
         flat = x.reshape(-1, H)
-        weights, idx = ops.moe_topk_router(self.gate(flat), self.top_k)
-        weights = weights.to(x.dtype)
+        kind = None
         if (flat.is_cuda and flat.dtype == torch.bfloat16
                 and not torch.is_grad_enabled() and ops.extension_loaded()):
             kind = self._fused_kind()
-            if kind is not None:
-                out = self._fused_forward(flat, weights, idx, kind)
-                return out.reshape(B, S, H)
+        if kind is not None and self._use_fused_router(H):
+            idx, weights, _ = ops.moe_route(flat, self.gate.weight,
+                                            self.top_k)
+            out = self._fused_forward(flat, weights, idx, kind)
+            return out.reshape(B, S, H)
+        weights, idx = ops.moe_topk_router(self.gate(flat), self.top_k)
+        weights = weights.to(x.dtype)
+        if kind is not None:
+            out = self._fused_forward(flat, weights, idx, kind)
+            return out.reshape(B, S, H)
         out = torch.zeros_like(flat)
         for e in range(self.num_experts):
             mask = (idx == e)

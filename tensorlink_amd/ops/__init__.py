@@ -843,6 +843,70 @@ def sample_token(logits, *, temperature=1.0, top_p=1.0, top_k=0,
 
 
 moe_topk_router = ref.moe_topk_router
+
+# ---------------------------------------------------------------------------
+# MoE routing (ops/csrc/moe_route.hip)
+# ---------------------------------------------------------------------------
+# incremented whenever moe_route.hip takes a call (same purpose as
+# gemm_dispatch_count: a silent fallback cannot pass as kernel coverage)
+moe_plan_dispatch_count = 0
+moe_combine_dispatch_count = 0
+moe_route_dispatch_count = 0
+
+
+def moe_plan_served(T: int, k: int, E: int, H: int) -> bool:
+    """Shapes the plan and combine kernels take; anything else keeps the
+    torch glue in MoEMLP._fused_forward."""
+    return T >= 1 and 1 <= k <= 8 and 1 <= E <= 128 and H % 8 == 0
+
+
+def moe_route_served(H: int, E: int, k: int) -> bool:
+    return H % 32 == 0 and 1 <= E <= 128 and 1 <= k <= min(8, E)
+
+
+def moe_plan(idx: torch.Tensor, num_experts: int):
+    """Dispatch plan of a routing, GPU only: idx [T, k] int64 or int32 ->
+    (seg_off [E+1], pair_tok [P], pos [T, k]) int32. The P = T * k pairs
+    are sorted by expert, stably: within an expert they ascend by
+    p = t * k + s, so the three equal idx.view(-1).argsort(stable=True)
+    // k, the cumulated bincount and the inverse permutation. Expert ids
+    are clamped into [0, E). No host sync, no atomics on global memory,
+    hipGraph-capturable."""
+    global moe_plan_dispatch_count
+    out = _require_ext().moe_plan(idx.contiguous(), num_experts)
+    moe_plan_dispatch_count += 1
+    return tuple(out)
+
+
+def moe_combine(y_pairs: torch.Tensor, weights: torch.Tensor,
+                pos: torch.Tensor) -> torch.Tensor:
+    """out[t] = bf16(sum_s float(bf16(y_pairs[pos[t, s]] * weights[t, s])))
+    with the sum in fp32, s ascending from 0: the MoE block's deterministic
+    combine, GPU only. y_pairs [P, H] bf16 (H % 8 == 0), weights [T, k]
+    bf16 in token order, pos [T, k] int32 from moe_plan."""
+    global moe_combine_dispatch_count
+    out = _require_ext().moe_combine(y_pairs.contiguous(),
+                                     weights.contiguous(), pos)
+    moe_combine_dispatch_count += 1
+    return out
+
+
+def moe_route(x: torch.Tensor, gate_weight: torch.Tensor, top_k: int):
+    """Fused router, GPU only: (idx int32 [T, k], weights bf16 [T, k],
+    logits bf16 [T, E]) from x [T, H] and gate_weight [E, H], both bf16,
+    H % 32 == 0, E <= 128, k <= min(8, E). The logits are bf16(x @ W^T)
+    summed in an order that depends on (H, E) only, so a token's routing is
+    bitwise the same in every batch; top-k is taken on the logits (greater
+    value first, then the smaller expert index) and the weights are the
+    softmax over the selected logits, which is the reference router's
+    softmax-then-renormalise."""
+    global moe_route_dispatch_count
+    out = _require_ext().moe_gate_topk(x.contiguous(),
+                                       gate_weight.contiguous(), top_k)
+    moe_route_dispatch_count += 1
+    return tuple(out)
+
+
 causal_lm_loss = ref.causal_lm_loss
 rope_cos_sin = ref.rope_cos_sin
 

@@ -93,6 +93,14 @@ void tl_mxfp4_moe_gemm(const void* x, const void* tok_idx,
                        const void* e_ptrs, void* out, void* partial, int T,
                        int P, int E, int N, int K, int n_split,
                        hipStream_t stream);
+void tl_moe_plan(const void* idx, int idx64, void* blk, void* seg_off,
+                 void* pair_tok, void* pos, int P, int E, int k,
+                 hipStream_t stream);
+void tl_moe_combine(const void* y, const void* w, const void* pos, void* out,
+                    int T, int H, int k, hipStream_t stream);
+void tl_moe_gate_topk(const void* x, const void* gw, void* idx, void* w,
+                      void* logits, int T, int H, int E, int k,
+                      hipStream_t stream);
 void tl_prefill_attn_lse(const void* q, const void* k, const void* v,
                          void* out, void* lse, int B, int Sq, int Skv,
                          int q_off, int Hq, int Hkv, int D, float scale,
@@ -1087,9 +1095,95 @@ Tensor mxfp4_moe_gemm(Tensor x, c10::optional<Tensor> tok_idx,
   return out;
 }
 
+// MoE routing (moe_route.hip). No call here syncs with the host, and every
+// buffer allocated is an output or a scratch its kernels write in full.
+
+// idx [T, k] int64 or int32, read as given -> (seg_off [E+1], pair_tok [P],
+// pos [T, k]) int32, the stable expert sort of the P = T * k pairs.
+std::vector<Tensor> moe_plan(Tensor idx, int64_t E) {
+  TORCH_CHECK(idx.is_cuda() && idx.is_contiguous() && idx.dim() == 2,
+              "idx must be a contiguous [T, k] GPU tensor");
+  const bool i64 = idx.scalar_type() == torch::kLong;
+  TORCH_CHECK(i64 || idx.scalar_type() == torch::kInt,
+              "idx must be int64 or int32");
+  const int64_t T = idx.size(0), k = idx.size(1);
+  TORCH_CHECK(E >= 1 && E <= 128 && k >= 1 && k <= 8 && T >= 1,
+              "moe_plan serves 1 <= E <= 128, 1 <= k <= 8, T >= 1");
+  const int64_t P = T * k;
+  TORCH_CHECK(P < ((int64_t)1 << 31) - 1024, "moe_plan: call too large");
+  auto opt = idx.options().dtype(torch::kInt);
+  auto seg_off = torch::empty({E + 1}, opt);
+  auto pair_tok = torch::empty({P}, opt);
+  auto pos = torch::empty({T, k}, opt);
+  const int64_t nblk = (P + 1023) / 1024;
+  Tensor blk;
+  void* bp = nullptr;
+  if (nblk > 1) {
+    blk = torch::empty({nblk * E}, opt);
+    bp = blk.data_ptr();
+  }
+  tl_moe_plan(idx.data_ptr(), i64 ? 1 : 0, bp, seg_off.data_ptr(),
+              pair_tok.data_ptr(), pos.data_ptr(), (int)P, (int)E, (int)k,
+              cur_stream());
+  return {seg_off, pair_tok, pos};
+}
+
+// out[t] = bf16(sum_s float(bf16(y_pairs[pos[t, s]] * weights[t, s]))),
+// fp32 sum, s ascending.
+Tensor moe_combine(Tensor y_pairs, Tensor weights, Tensor pos) {
+  CHECK_IN(y_pairs, torch::kBFloat16);
+  CHECK_IN(weights, torch::kBFloat16);
+  CHECK_IN(pos, torch::kInt);
+  TORCH_CHECK(y_pairs.dim() == 2 && weights.dim() == 2 && pos.dim() == 2,
+              "y_pairs must be [P, H], weights and pos [T, k]");
+  const int64_t P = y_pairs.size(0), H = y_pairs.size(1);
+  const int64_t T = pos.size(0), k = pos.size(1);
+  TORCH_CHECK(weights.size(0) == T && weights.size(1) == k && P == T * k,
+              "moe_combine: shapes disagree");
+  TORCH_CHECK(H >= 8 && H % 8 == 0 && k >= 1 && k <= 8 && T >= 1,
+              "moe_combine serves H % 8 == 0, 1 <= k <= 8, T >= 1");
+  TORCH_CHECK(P < (int64_t)1 << 31 && H < (1 << 24),
+              "moe_combine: call too large");
+  TORCH_CHECK(weights.device() == y_pairs.device() &&
+                  pos.device() == y_pairs.device(),
+              "operands must share a device");
+  auto out = torch::empty({T, H}, y_pairs.options());
+  tl_moe_combine(y_pairs.data_ptr(), weights.data_ptr(), pos.data_ptr(),
+                 out.data_ptr(), (int)T, (int)H, (int)k, cur_stream());
+  return out;
+}
+
+// x [T, H], gate_w [E, H] bf16 -> (idx int32 [T, k], weights bf16 [T, k],
+// logits bf16 [T, E]).
+std::vector<Tensor> moe_gate_topk(Tensor x, Tensor gate_w, int64_t k) {
+  CHECK_IN(x, torch::kBFloat16);
+  CHECK_IN(gate_w, torch::kBFloat16);
+  TORCH_CHECK(x.dim() == 2 && gate_w.dim() == 2, "x [T, H], gate_w [E, H]");
+  const int64_t T = x.size(0), H = x.size(1), E = gate_w.size(0);
+  TORCH_CHECK(gate_w.size(1) == H, "H mismatch");
+  TORCH_CHECK(gate_w.device() == x.device(), "operands must share a device");
+  TORCH_CHECK(H >= 32 && H % 32 == 0 && H < (1 << 24) && E >= 1 &&
+                  E <= 128 && k >= 1 && k <= 8 && k <= E && T >= 1,
+              "moe_gate_topk serves H % 32 == 0, E <= 128, k <= min(8, E)");
+  TORCH_CHECK(T * 128 < (int64_t)1 << 31, "moe_gate_topk: call too large");
+  auto idx = torch::empty({T, k}, x.options().dtype(torch::kInt));
+  auto w = torch::empty({T, k}, x.options());
+  auto logits = torch::empty({T, E}, x.options());
+  tl_moe_gate_topk(x.data_ptr(), gate_w.data_ptr(), idx.data_ptr(),
+                   w.data_ptr(), logits.data_ptr(), (int)T, (int)H, (int)E,
+                   (int)k, cur_stream());
+  return {idx, w, logits};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
+  mod.def("moe_plan", &moe_plan,
+          "stable expert sort of (token, slot) pairs: seg_off, pair_tok, pos");
+  mod.def("moe_combine", &moe_combine,
+          "weighted fixed-slot-order combine of expert-sorted pair rows");
+  mod.def("moe_gate_topk", &moe_gate_topk,
+          "fused router: gate GEMM, top-k on the logits, renormalised weights");
   mod.def("rope_append_", &rope_append_,
           "fused RoPE + KV-cache append from fused-QKV rows");
   mod.def("swiglu_fused", &swiglu_fused, "silu-mul on fused [.,2I] rows");
