@@ -25,13 +25,57 @@ def timeit(fn, iters=50):
     return (time.perf_counter() - t0) / iters * 1e6  # us
 
 
+def colbal_sk(csv):
+    """The decode split-K GEMMs at M = 128 / 256 / 512: gemm_tiled_kernel's
+    partials (the routing switched off) against gemm_colbal_sk's, isolated,
+    with a digest of the partial tensor from both."""
+    import hashlib
+    C = ops._require_ext()
+    rows = []
+    for name, N, K in (("qkv", 4608, 3584), ("o", 3584, 3584),
+                       ("down", 3584, 18944)):
+        w = torch.randn(N, K, device="cuda", dtype=torch.bfloat16) / K ** 0.5
+        for M in (128, 256, 512):
+            x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
+            os.environ["TL_NO_COLBAL_SK"] = "1"
+            t_tiled = timeit(lambda: C.skinny_gemm_partials(x, w, None))
+            want = C.skinny_gemm_partials(x, w, None)
+            os.environ.pop("TL_NO_COLBAL_SK")
+            t_sk = timeit(lambda: C.gemm_colbal_sk(x, w))
+            got = C.gemm_colbal_sk(x, w)
+            same = torch.equal(got.view(torch.int32), want.view(torch.int32))
+            dig = [hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()[:16]
+                   for t in (want, got)]
+            wb = N * K * 2 / 1e9
+            fl = 2.0 * M * N * K / 1e12
+            print(f"{name:5s} M{M:4d} N{N:5d} K{K:6d} n_split "
+                  f"{C.gemm_n_split(N, K)}: tiled {t_tiled:6.1f}us "
+                  f"({wb / t_tiled * 1e3:4.2f} TB/s {fl / t_tiled * 1e6:4.0f}"
+                  f" TF)  colbal_sk {t_sk:6.1f}us ({wb / t_sk * 1e3:4.2f} "
+                  f"TB/s {fl / t_sk * 1e6:4.0f} TF)  bits equal {same}  "
+                  f"sha256 {dig[0]} / {dig[1]}", flush=True)
+            rows.append((name, M, N, K, t_tiled, t_sk, same, dig[0], dig[1]))
+    if csv:
+        os.makedirs(os.path.dirname(csv), exist_ok=True)
+        with open(csv, "w") as f:
+            f.write("name,M,N,K,tiled_us,colbal_sk_us,bits_equal,"
+                    "sha_tiled,sha_colbal_sk\n")
+            for r in rows:
+                f.write(",".join(str(v) for v in r) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--csv", default=None)
+    ap.add_argument("--colbal-sk", action="store_true",
+                    help="only the decode split-K shapes (qkv, o, down at "
+                         "M=128/256/512): gemm_tiled against gemm_colbal_sk")
     ap.add_argument("--colbal", action="store_true",
                     help="only the shapes the column-balanced kernel "
                          "serves (gate_up at M=128/256/512, lm_head)")
     args = ap.parse_args()
+    if args.colbal_sk:
+        return colbal_sk(args.csv)
     C = ops._require_ext()
     rows = []
     shapes = [

@@ -63,6 +63,10 @@ void tl_gemm_tiled(const void* x, const void* w, const void* bias, void* out,
                    int reduce, hipStream_t stream);
 void tl_gemm_colbal(const void* x, const void* w, void* out, int M, int N,
                     int K, int n_blocks, int fused, hipStream_t stream);
+void tl_gemm_colbal_sk(const void* x, const void* w, const void* bias,
+                       void* out, void* partial, int M, int N, int K,
+                       int n_split, int n_blocks, int reduce,
+                       hipStream_t stream);
 void tl_head_argmax(const void* x, const void* w, void* best, void* tok,
                     int M, int N, int K, hipStream_t stream);
 void tl_head_ce_stats(const void* x, const void* w, const void* labels,
@@ -590,8 +594,51 @@ static std::vector<std::pair<int, int>> gemm_k_slices(int K, int n_split) {
   return out;
 }
 
+// CU count of a device, read once: the column-balanced GEMMs launch one
+// workgroup per CU (gemm_colbal.hip, gemm_colbal_sk.hip).
+static int device_cu_count(int dev) {
+  static int cus[64] = {0};
+  TORCH_CHECK(dev >= 0 && dev < 64, "device index out of range");
+  if (cus[dev] == 0) {
+    int n = 0;
+    TORCH_CHECK(hipDeviceGetAttribute(
+                    &n, hipDeviceAttributeMultiprocessorCount, dev) ==
+                        hipSuccess && n > 0,
+                "cannot read the CU count");
+    cus[dev] = n;
+  }
+  return cus[dev];
+}
+
+// The column ranges of the column-balanced decomposition (colbal_range,
+// colbal_sub_range of gemm_policy.hpp, which gemm_colbal_sk.hip walks): for
+// each of G workgroups the (first tile, tiles) of its sub-ranges at `slots`
+// tiles per pass. Host arithmetic only.
+static std::vector<std::vector<std::pair<int, int>>> colbal_ranges(
+    int T, int G, int slots) {
+  TORCH_CHECK(T >= 1 && G >= 1 && slots >= 1, "unsupported shape");
+  std::vector<std::vector<std::pair<int, int>>> out(G);
+  for (int b = 0; b < G; ++b) {
+    const TileRange r = colbal_range(T, G, b);
+    for (int s = 0; s < colbal_n_sub(r.count, slots); ++s) {
+      const TileRange sub = colbal_sub_range(r, slots, s);
+      out[b].emplace_back(sub.start, sub.count);
+    }
+  }
+  return out;
+}
+
+static std::vector<int> colbal_sk_slot_counts() {
+  return std::vector<int>(std::begin(TL_COLBAL_SK_SLOTS),
+                          std::end(TL_COLBAL_SK_SLOTS));
+}
+
 // x @ W^T (+ bias) through the streaming (M <= TL_GEMM_STREAM_M) or tiled
-// kernel. reduce: the bf16 output [.., N]. !reduce: the fp32 split-K
+// kernel, or, for the split (class, M band) pairs of colbal_sk_routed, the
+// split-K column-balanced kernel: the same partials, bit for bit, so the
+// choice shows nowhere but in the time. TL_NO_COLBAL_SK=1, read per call,
+// keeps those on the tiled kernel for A/B runs and tests.
+// reduce: the bf16 output [.., N]. !reduce: the fp32 split-K
 // partials [n_split, .., N] for a consumer kernel to sum (s order from 0,
 // then bias, then one bf16 rounding — exactly what the reduce kernel does),
 // so bias is NOT applied; when the policy gives n_split == 1 there is
@@ -624,11 +671,64 @@ static Tensor family_gemm(Tensor x, Tensor w, c10::optional<Tensor> bias,
       partial = torch::empty({(int64_t)n_split * M * N},
                              x.options().dtype(torch::kFloat));
   }
+  if (colbal_sk_routed((int)M, N, K, n_split) &&
+      !std::getenv("TL_NO_COLBAL_SK")) {
+    const int g = colbal_sk_blocks(N / 16, n_split,
+                                   device_cu_count(x.get_device()));
+    tl_gemm_colbal_sk(x.data_ptr(), w.data_ptr(), bp,
+                      hand_out ? nullptr : out.data_ptr(), partial.data_ptr(),
+                      (int)M, N, K, n_split, g, hand_out ? 0 : 1,
+                      cur_stream());
+    return hand_out ? partial : out;
+  }
   auto launch = M <= TL_GEMM_STREAM_M ? tl_skinny_gemm : tl_gemm_tiled;
   launch(x.data_ptr(), w.data_ptr(), bp, hand_out ? nullptr : out.data_ptr(),
          n_split > 1 ? partial.data_ptr() : nullptr, (int)M, N, K, n_split,
          hand_out ? 0 : 1, cur_stream());
   return hand_out ? partial : out;
+}
+
+// The split-K partials [n_split, .., N] fp32 from the column-balanced
+// kernel, whatever the routing says, for any M >= 1 of a shape the policy
+// splits. n_blocks (workgroups per split and 256-row block) defaults to
+// colbal_sk_blocks; the bits do not depend on it, tests use it to force
+// uneven, multi-pass and empty column ranges. `into`: a contiguous fp32
+// tensor of at least n_split * M * N elements to write the partials to (a
+// test poisons it first); the result is then a view of its head.
+Tensor gemm_colbal_sk(Tensor x, Tensor w, int64_t n_blocks,
+                      c10::optional<Tensor> into) {
+  CHECK_IN(x, torch::kBFloat16);
+  CHECK_IN(w, torch::kBFloat16);
+  const int K = x.size(-1);
+  const int64_t M = x.numel() / K;
+  const int N = w.size(0);
+  TORCH_CHECK(w.dim() == 2 && w.size(1) == K, "K mismatch");
+  TORCH_CHECK(K % 32 == 0 && K >= 32 && M >= 1 && M < (1 << 24) &&
+                  N % 16 == 0 && N > 0,
+              "unsupported shape");
+  const int n_split = gemm_n_split(N, K);
+  TORCH_CHECK(n_split > 1,
+              "gemm_colbal_sk serves only shapes the policy splits");
+  if (n_blocks <= 0)
+    n_blocks = colbal_sk_blocks(N / 16, n_split,
+                                device_cu_count(x.get_device()));
+  TORCH_CHECK(n_blocks <= 65535, "n_blocks too large");
+  auto sizes = x.sizes().vec();
+  sizes.back() = N;
+  sizes.insert(sizes.begin(), n_split);
+  Tensor partial;
+  if (into.has_value()) {
+    CHECK_IN(into.value(), torch::kFloat);
+    TORCH_CHECK(into->numel() >= (int64_t)n_split * M * N, "into too small");
+    partial = into->view({-1}).narrow(0, 0, (int64_t)n_split * M * N)
+                  .view(sizes);
+  } else {
+    partial = torch::empty(sizes, x.options().dtype(torch::kFloat));
+  }
+  tl_gemm_colbal_sk(x.data_ptr(), w.data_ptr(), nullptr, nullptr,
+                    partial.data_ptr(), (int)M, N, K, n_split, (int)n_blocks,
+                    0, cur_stream());
+  return partial;
 }
 
 Tensor skinny_gemm(Tensor x, Tensor w, c10::optional<Tensor> bias) {
@@ -637,22 +737,6 @@ Tensor skinny_gemm(Tensor x, Tensor w, c10::optional<Tensor> bias) {
 
 Tensor skinny_gemm_partials(Tensor x, Tensor w, c10::optional<Tensor> bias) {
   return family_gemm(x, w, bias, false);
-}
-
-// CU count of a device, read once: the column-balanced GEMM launches one
-// workgroup per CU (gemm_colbal.hip).
-static int device_cu_count(int dev) {
-  static int cus[64] = {0};
-  TORCH_CHECK(dev >= 0 && dev < 64, "device index out of range");
-  if (cus[dev] == 0) {
-    int n = 0;
-    TORCH_CHECK(hipDeviceGetAttribute(
-                    &n, hipDeviceAttributeMultiprocessorCount, dev) ==
-                        hipSuccess && n > 0,
-                "cannot read the CU count");
-    cus[dev] = n;
-  }
-  return cus[dev];
 }
 
 // Column-balanced one-pass GEMM (gemm_colbal.hip): x @ W^T for the wide
@@ -1198,6 +1282,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("gemm_colbal_swiglu", &gemm_colbal_swiglu,
           "column-balanced gate_up GEMM with SwiGLU on the accumulators",
           py::arg("x"), py::arg("w_gate_up"), py::arg("n_blocks") = 0);
+  mod.def("gemm_colbal_sk", &gemm_colbal_sk,
+          "column-balanced split-K GEMM: the fp32 partials [n_split, .., N]",
+          py::arg("x"), py::arg("w"), py::arg("n_blocks") = 0,
+          py::arg("into") = py::none());
+  mod.def("colbal_ranges", &colbal_ranges,
+          "per workgroup, the (first tile, tiles) of its column sub-ranges",
+          py::arg("T"), py::arg("G"), py::arg("slots"));
+  mod.def("colbal_sk_slot_counts", &colbal_sk_slot_counts,
+          "slot counts gemm_colbal_sk is built with");
+  mod.def(
+      "colbal_sk_routed",
+      [](int M, int N, int K) {
+        return colbal_sk_routed(M, N, K, gemm_n_split(N, K)) &&
+               !std::getenv("TL_NO_COLBAL_SK");
+      },
+      "whether skinny_gemm / skinny_gemm_partials take gemm_colbal_sk at "
+      "this (M, N, K) now");
   mod.def("lm_head_argmax", &lm_head_argmax,
           "fused greedy head: argmax of bf16(x @ W^T) without the logits");
   mod.def("head_ce_stats", &head_ce_stats,

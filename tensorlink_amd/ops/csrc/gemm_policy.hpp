@@ -67,6 +67,66 @@ TL_HD inline KSlice gemm_k_slice(int K, int n_split, int split) {
   return {begin, K < begin + per ? K : begin + per};
 }
 
+// Column-balanced decomposition (gemm_colbal_sk.hip): the T = N / 16 column
+// tiles are dealt to G workgroups in contiguous ranges balanced by COUNT —
+// the first T % G get ceil(T / G), the rest floor(T / G) — and a range is
+// walked in equalised sub-ranges of at most `slots` tiles, the width one
+// LDS stage holds. None of it reaches the bits: every output element is
+// one K chain whoever computes it.
+struct TileRange {
+  int start, count;
+};
+
+TL_HD inline TileRange colbal_range(int T, int G, int b) {
+  const int q = T / G, r = T % G;
+  return {b * q + (b < r ? b : r), q + (b < r ? 1 : 0)};
+}
+
+TL_HD inline int colbal_n_sub(int count, int slots) {
+  return (count + slots - 1) / slots;
+}
+
+// sub-range s of the colbal_n_sub(range.count, slots) of `range`
+TL_HD inline TileRange colbal_sub_range(TileRange range, int slots, int s) {
+  const TileRange sub =
+      colbal_range(range.count, colbal_n_sub(range.count, slots), s);
+  return {range.start + sub.start, sub.count};
+}
+
+// Slot counts the split-K column-balanced kernel is built with, and the one
+// a launch takes: the smallest that holds a workgroup's range in one pass,
+// else the largest.
+constexpr int TL_COLBAL_SK_SLOTS[] = {5, 7};
+
+inline int colbal_sk_slots(int T, int G) {
+  const int widest = (T + G - 1) / G;
+  for (int s : TL_COLBAL_SK_SLOTS)
+    if (widest <= s) return s;
+  return 7;
+}
+
+// Workgroups per split: the splits share the CUs, one workgroup each, and
+// no workgroup is launched for nothing.
+inline int colbal_sk_blocks(int T, int n_split, int cus) {
+  const int g = cus / n_split;
+  return g < 1 ? 1 : g > T ? T : g;
+}
+
+// The (class, M band) pairs the split-K column-balanced kernel serves: those
+// where the in-pipeline trace shows it ahead of gemm_tiled_kernel
+// (profiles/gemm_colbal_sk.md §2). The kernel may depend on M because the
+// bits do not; the split count may not. Classes as ops/__init__.py names
+// them: deepk is K >= 8192, narrow the rest below the gateup widths.
+inline bool colbal_sk_routed(int M, int N, int K, int n_split) {
+  if (n_split <= 1 || N >= TL_GEMM_WIDE_N || N % 16 != 0) return false;
+  if (M <= TL_GEMM_STREAM_M || M > 512) return false;
+  const bool deepk = K >= 8192;
+  const int band = M <= 128 ? 0 : M <= 256 ? 1 : 2;
+  constexpr bool narrow_on[3] = {true, true, true};
+  constexpr bool deepk_on[3] = {true, true, true};
+  return deepk ? deepk_on[band] : narrow_on[band];
+}
+
 // Split-K count of the MXFP4 kernels, counted in their 128-k steps: a
 // column's packed bytes are 4x fewer than bf16, so a split keeps >= 2
 // steps. `blocks` is the grid before the split: N/64 for mxfp4_gemm (pure
