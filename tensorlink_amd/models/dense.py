@@ -147,7 +147,15 @@ class Attention(nn.Module):
         B, S, H = x.shape
         eps = self.config.rms_norm_eps
         fuse = fuse and kv_cache is not None and not training
-        if fuse and not self.use_qk_norm:
+        # qk-norm (Qwen3), cached inference: the per-head norms run inside
+        # the rope+append kernel (ops/csrc/qknorm_rope_append.hip), so the
+        # projection can hand over partials like every other family.
+        # TL_NO_QKNORM_FUSION=1 (read per call) keeps the split / norm /
+        # cat chain below, as do head sizes the kernel does not take.
+        qk_fused = (self.use_qk_norm and self.head_dim in (64, 128)
+                    and kv_cache is not None and not training
+                    and os.environ.get("TL_NO_QKNORM_FUSION") != "1")
+        if fuse and (qk_fused or not self.use_qk_norm):
             qkv = _project(self.qkv_proj, x, allow_bias=True)
         else:
             qkv = self.qkv_proj(x)
@@ -180,7 +188,11 @@ class Attention(nn.Module):
         # fused-QKV rows (q comes back contiguous, k/v land in the cache;
         # paged caches pass their block table through to the kernels)
         table = getattr(kv_cache, "table", None)
-        if self.use_qk_norm:
+        norms = {}
+        if qk_fused:
+            norms = dict(q_norm=self.q_norm.to(x.dtype),
+                         k_norm=self.k_norm.to(x.dtype), eps=eps)
+        elif self.use_qk_norm:
             q, k, v = self._split_qkv(qkv, B, S)
             q = ops.rmsnorm(q.contiguous(), self.q_norm.to(q.dtype), eps)
             k = ops.rmsnorm(k.contiguous(), self.k_norm.to(k.dtype), eps)
@@ -190,7 +202,8 @@ class Attention(nn.Module):
             qkv = qkv.reshape(B * S, -1)
         q = ops.rope_append_(qkv, kv_cache.k[layer_idx],
                              kv_cache.v[layer_idx], flat_pos, self.inv_freq,
-                             S, self.n_heads, self.n_kv, block_table=table)
+                             S, self.n_heads, self.n_kv, block_table=table,
+                             **norms)
         q = q.view(B, S, self.n_heads, self.head_dim)
         if S == 1 and fuse:
             out = ops.attention_decode(

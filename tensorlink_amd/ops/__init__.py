@@ -178,10 +178,18 @@ def apply_rope_(q: torch.Tensor, k: torch.Tensor, positions: torch.Tensor,
     _require_ext().rope_(q, k, positions.int(), inv_freq.float(), sign)
 
 
+# incremented whenever the qk-norm kernel handles a call (same purpose as
+# gemm_dispatch_count: a silent fallback cannot pass as kernel coverage)
+qknorm_rope_dispatch_count = 0
+
+
 def rope_append_(qkv, k_cache: torch.Tensor,
                  v_cache: torch.Tensor, positions: torch.Tensor,
                  inv_freq: torch.Tensor, S: int, Hq: int, Hkv: int,
-                 block_table: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 block_table: Optional[torch.Tensor] = None, *,
+                 q_norm: Optional[torch.Tensor] = None,
+                 k_norm: Optional[torch.Tensor] = None,
+                 eps: float = 1e-6) -> torch.Tensor:
     """Fused RoPE + KV-cache append from the fused-QKV projection output.
 
     qkv [T, (Hq+2*Hkv)*D] with T = B*S (q | k | v per row); caches
@@ -192,12 +200,27 @@ def rope_append_(qkv, k_cache: torch.Tensor,
     qkv may be the projection's :class:`Partials` (reduced + biased
     in-kernel, same bits). inv_freq may be fp32 or bf16 — the kernel
     widens bf16 in-register, so no conversion kernel runs per call.
+
+    q_norm / k_norm [D] (both or neither; Qwen3): every q head and every
+    k head is RMS-normalised with its weight before the rotation. On the
+    GPU that is one launch of qknorm_rope_append.hip (D 64 or 128) with
+    the bits of rmsnorm per head followed by this op without weights; on
+    the CPU it is ref.rmsnorm per head in front of the path below.
     """
+    global qknorm_rope_dispatch_count
+    assert (q_norm is None) == (k_norm is None), "q_norm and k_norm pair"
     part = isinstance(qkv, Partials)
     if _on_gpu(k_cache):
         if inv_freq.dtype not in (torch.float32, torch.bfloat16):
             inv_freq = inv_freq.float()
         bt = block_table.int() if block_table is not None else None
+        if q_norm is not None:
+            qknorm_rope_dispatch_count += 1
+            return _require_ext().qknorm_rope_append_(
+                qkv.data if part else qkv.contiguous(), k_cache, v_cache,
+                positions.int(), inv_freq.contiguous(), S, Hq, Hkv,
+                q_norm.contiguous(), k_norm.contiguous(), eps, bt,
+                qkv.bias if part else None)
         if part:
             return _require_ext().rope_append_(
                 qkv.data, k_cache, v_cache, positions.int(),
@@ -212,6 +235,9 @@ def rope_append_(qkv, k_cache: torch.Tensor,
     q = qkv[..., :Hq * D].reshape(T, Hq, D).contiguous()
     k = qkv[..., Hq * D:(Hq + Hkv) * D].reshape(T, Hkv, D).contiguous()
     v = qkv[..., (Hq + Hkv) * D:].reshape(T, Hkv, D).contiguous()
+    if q_norm is not None:
+        q = ref.rmsnorm(q, q_norm, eps)
+        k = ref.rmsnorm(k, k_norm, eps)
     apply_rope_(q, k, positions, inv_freq)
     B = T // S
     pos = positions.view(B, S).long()

@@ -46,6 +46,14 @@ void tl_rope_append(const void* qkv, const void* bias, void* q_out,
                     int64_t T, int row_stride, int S, int Hq, int Hkv,
                     int D, int Smax, int bt_stride, int n_split,
                     int inv_bf16, hipStream_t stream);
+void tl_qknorm_rope_append(const void* qkv, const void* bias,
+                           const void* q_norm, const void* k_norm,
+                           void* q_out, void* k_cache, void* v_cache,
+                           const void* positions, const void* inv_freq,
+                           const void* block_table, int64_t T, int S, int Hq,
+                           int Hkv, int D, int Smax, int bt_stride,
+                           int n_split, int inv_bf16, float eps,
+                           int one_block, hipStream_t stream);
 void tl_swiglu_fused(const void* gu, void* out, int64_t N, int I,
                      hipStream_t stream);
 void tl_decode_attn_mfma(const void* q, const void* k_cache,
@@ -498,11 +506,17 @@ std::vector<Tensor> attn_bwd(Tensor q, Tensor k, Tensor v, Tensor dout,
 // (skinny_gemm_partials) with its bias passed alongside. inv_freq fp32 or
 // bf16. Returns rotated q as a contiguous [T, Hq, D] tensor; k/v land in
 // the caches.
-Tensor rope_append_(Tensor qkv, Tensor k_cache, Tensor v_cache,
-                    Tensor positions, Tensor inv_freq, int64_t S,
-                    int64_t Hq, int64_t Hkv,
-                    c10::optional<Tensor> block_table,
-                    c10::optional<Tensor> bias) {
+//
+// q_norm / k_norm non-null: qknorm_rope_append.hip normalises every q and k
+// head (bf16 weights [D], D 64 or 128) before the rotation, in the same
+// launch; same checks otherwise.
+static Tensor rope_append_impl(Tensor qkv, Tensor k_cache, Tensor v_cache,
+                               Tensor positions, Tensor inv_freq, int64_t S,
+                               int64_t Hq, int64_t Hkv,
+                               c10::optional<Tensor> block_table,
+                               c10::optional<Tensor> bias,
+                               const Tensor* q_norm, const Tensor* k_norm,
+                               double eps) {
   CHECK_IN(k_cache, torch::kBFloat16);
   CHECK_IN(v_cache, torch::kBFloat16);
   CHECK_IN(positions, torch::kInt);
@@ -521,7 +535,8 @@ Tensor rope_append_(Tensor qkv, Tensor k_cache, Tensor v_cache,
     CHECK_IN(qkv, torch::kFloat);
     TORCH_CHECK(qkv.dim() >= 2, "partials must be [n_split, T, width]");
     n_split = (int)qkv.size(0);
-    TORCH_CHECK(row_stride <= 32768, "qkv row too wide for the LDS stage");
+    TORCH_CHECK(q_norm || row_stride <= 32768,
+                "qkv row too wide for the LDS stage");
     if (bias.has_value()) {
       CHECK_IN(bias.value(), torch::kBFloat16);
       TORCH_CHECK(bias->numel() == row_stride, "bias size mismatch");
@@ -548,12 +563,54 @@ Tensor rope_append_(Tensor qkv, Tensor k_cache, Tensor v_cache,
     TORCH_CHECK(k_cache.size(0) * S == T, "cache batch mismatch");
   }
   auto q_out = torch::empty({T, Hq, (int64_t)D}, k_cache.options());
+  if (q_norm) {
+    TORCH_CHECK(D == 64 || D == 128, "qk-norm kernel takes D 64 or 128");
+    for (const Tensor* w : {q_norm, k_norm}) {
+      CHECK_IN(*w, torch::kBFloat16);
+      TORCH_CHECK(w->numel() == D, "norm weight must have D elements");
+      TORCH_CHECK((uintptr_t)w->data_ptr() % 16 == 0,
+                  "norm weight must be 16-byte aligned");
+    }
+    TORCH_CHECK((uintptr_t)qkv.data_ptr() % 16 == 0 &&
+                    (!bp || (uintptr_t)bp % 16 == 0),
+                "qkv and bias must be 16-byte aligned");
+    // TL_QKNORM_ONE_BLOCK=1, read per call: one block per token walks all
+    // head sweeps instead of one block per (token, sweep); same bits
+    const char* ob = std::getenv("TL_QKNORM_ONE_BLOCK");
+    tl_qknorm_rope_append(qkv.data_ptr(), bp, q_norm->data_ptr(),
+                          k_norm->data_ptr(), q_out.data_ptr(),
+                          k_cache.data_ptr(), v_cache.data_ptr(),
+                          positions.data_ptr(), inv_freq.data_ptr(), bt, T,
+                          (int)S, (int)Hq, (int)Hkv, D, Smax, bt_stride,
+                          n_split, inv_bf16 ? 1 : 0, (float)eps,
+                          (ob && ob[0] == '1') ? 1 : 0, cur_stream());
+    return q_out;
+  }
   tl_rope_append(qkv.data_ptr(), bp, q_out.data_ptr(), k_cache.data_ptr(),
                  v_cache.data_ptr(), positions.data_ptr(),
                  inv_freq.data_ptr(), bt, T, row_stride, (int)S, (int)Hq,
                  (int)Hkv, D, Smax, bt_stride, n_split, inv_bf16 ? 1 : 0,
                  cur_stream());
   return q_out;
+}
+
+Tensor rope_append_(Tensor qkv, Tensor k_cache, Tensor v_cache,
+                    Tensor positions, Tensor inv_freq, int64_t S,
+                    int64_t Hq, int64_t Hkv,
+                    c10::optional<Tensor> block_table,
+                    c10::optional<Tensor> bias) {
+  return rope_append_impl(qkv, k_cache, v_cache, positions, inv_freq, S, Hq,
+                          Hkv, block_table, bias, nullptr, nullptr, 0.0);
+}
+
+Tensor qknorm_rope_append_(Tensor qkv, Tensor k_cache, Tensor v_cache,
+                           Tensor positions, Tensor inv_freq, int64_t S,
+                           int64_t Hq, int64_t Hkv, Tensor q_norm,
+                           Tensor k_norm, double eps,
+                           c10::optional<Tensor> block_table,
+                           c10::optional<Tensor> bias) {
+  return rope_append_impl(qkv, k_cache, v_cache, positions, inv_freq, S, Hq,
+                          Hkv, block_table, bias, &q_norm, &k_norm, eps);
 }
 
 Tensor swiglu_fused(Tensor gu) {
@@ -1270,6 +1327,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "fused router: gate GEMM, top-k on the logits, renormalised weights");
   mod.def("rope_append_", &rope_append_,
           "fused RoPE + KV-cache append from fused-QKV rows");
+  mod.def("qknorm_rope_append_", &qknorm_rope_append_,
+          "per-head q/k RMSNorm + RoPE + KV-cache append in one launch");
   mod.def("swiglu_fused", &swiglu_fused, "silu-mul on fused [.,2I] rows");
   mod.def("skinny_gemm", &skinny_gemm, "decode-M GEMM: x @ W^T + bias");
   mod.def("gemm_n_split", &gemm_n_split,
