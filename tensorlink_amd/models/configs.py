@@ -46,6 +46,9 @@ class ModelConfig:
     # GPT-NeoX: fraction of each head rotated by RoPE; parallel residual
     rotary_pct: float = 1.0
     use_parallel_residual: bool = True
+    # sliding-window attention (Mistral / Mixtral): every layer's query at
+    # position p sees keys (p - sliding_window, p]. 0 = full causal.
+    sliding_window: int = 0
     # architecture tag for checkpoint key mapping
     architecture: str = "llama"
 
@@ -134,6 +137,21 @@ class ModelConfig:
         if any("GPTNeoX" in a for a in archs):
             arch = "neox"
         get = cfg.get
+        # Qwen windows only the layers past max_window_layers; a per-layer
+        # window is not built, and serving such a config with full (or
+        # all-layer windowed) attention would be silently wrong
+        if arch in ("qwen2", "qwen3") and get("use_sliding_window", False):
+            raise KeyError(
+                f"unsupported config for {archs}: use_sliding_window=true "
+                "(per-layer windows via max_window_layers) is not "
+                "implemented; sliding-window attention covers Mistral and "
+                "Mixtral, where one window applies to every layer")
+        sw = get("sliding_window", None)
+        window = 0
+        if (any(k in a for a in archs for k in ("Mistral", "Mixtral"))
+                and isinstance(sw, int) and not isinstance(sw, bool)
+                and sw > 0):
+            window = sw
         return cls(
             name=name,
             vocab_size=get("vocab_size", 32000),
@@ -157,6 +175,7 @@ class ModelConfig:
             rope_scaling=get("rope_scaling", None),
             rotary_pct=get("rotary_pct", 1.0) or 1.0,
             use_parallel_residual=get("use_parallel_residual", True),
+            sliding_window=window,
             architecture=arch,
         )
 

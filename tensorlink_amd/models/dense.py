@@ -147,6 +147,9 @@ class Attention(nn.Module):
         B, S, H = x.shape
         eps = self.config.rms_norm_eps
         fuse = fuse and kv_cache is not None and not training
+        # sliding window (Mistral): 0 = none. The cache keeps every token;
+        # the kernels read only the window.
+        window = self.config.sliding_window
         # qk-norm (Qwen3), cached inference: the per-head norms run inside
         # the rope+append kernel (ops/csrc/qknorm_rope_append.hip), so the
         # projection can hand over partials like every other family.
@@ -173,7 +176,7 @@ class Attention(nn.Module):
                 q = q2.view(B, S, self.n_heads, -1)
                 k = k2.view(B, S, self.n_kv, -1)
                 out = ops.attention_train(q, k, v, causal=True,
-                                          scale=self.scale)
+                                          scale=self.scale, window=window)
             else:
                 q = q.contiguous()
                 k = k.contiguous()
@@ -181,7 +184,8 @@ class Attention(nn.Module):
                                 k.view(B * S, self.n_kv, -1), flat_pos,
                                 self.inv_freq)
                 out = ops.attention_prefill(q, k, v.contiguous(),
-                                            causal=True, scale=self.scale)
+                                            causal=True, scale=self.scale,
+                                            window=window)
             return self.o_proj(out.reshape(B, S, -1))
 
         # inference with KV cache: fused rope+append straight off the
@@ -209,11 +213,12 @@ class Attention(nn.Module):
             out = ops.attention_decode(
                 q, kv_cache.k[layer_idx], kv_cache.v[layer_idx],
                 kv_cache.seq_lens, scale=self.scale, block_table=table,
-                len_add=1)
+                len_add=1, window=window)
         elif S == 1:
             out = ops.attention_decode(
                 q, kv_cache.k[layer_idx], kv_cache.v[layer_idx],
-                kv_cache.seq_lens + 1, scale=self.scale, block_table=table)
+                kv_cache.seq_lens + 1, scale=self.scale, block_table=table,
+                window=window)
         else:
             # prefill with cache write; rotated k / raw v are read back from
             # the cache. off > 0 = chunked prefill continuing an existing
@@ -237,7 +242,8 @@ class Attention(nn.Module):
             else:
                 k_attn, v_attn = kv_cache.gather_contiguous(layer_idx, kv_len)
             out = ops.attention_prefill(q, k_attn, v_attn, causal=True,
-                                        scale=self.scale, q_off=off)
+                                        scale=self.scale, q_off=off,
+                                        window=window)
         if fuse:
             return _project(self.o_proj, out.reshape(B, S, -1))
         return self.o_proj(out.reshape(B, S, -1))

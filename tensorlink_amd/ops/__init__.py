@@ -320,14 +320,21 @@ def swiglu_fused(gate_up: torch.Tensor) -> torch.Tensor:
 # ---------------------------------------------------------------------------
 def attention_prefill(q, k, v, causal: bool = True,
                       scale: Optional[float] = None,
-                      q_off: int = 0) -> torch.Tensor:
+                      q_off: int = 0, window: int = 0) -> torch.Tensor:
     """q [B,Sq,Hq,D], k/v [B,Skv,Hkv,D] -> [B,Sq,Hq,D]. Inference path.
     q_off: query row i is at global position q_off+i (chunked prefill).
-    k/v may be views with any batch/token/head strides (D contiguous)."""
+    k/v may be views with any batch/token/head strides (D contiguous).
+    window > 0 (causal only): sliding-window attention, the row at global
+    position p sees key j iff p - window < j <= p. On the GPU it always
+    runs the windowed instantiation of the HIP kernel, at every length: the
+    library path below cannot express a band. 0 = no window."""
+    global attn_window_dispatch_count
     scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    if window < 0 or (window and not causal):
+        raise ValueError("window must be >= 0 and requires causal")
     if not _on_gpu(q):
-        return ref.attention_prefill(q, k, v, causal, scale, q_off)
-    if (q.shape[1] >= 4096 and q_off == 0 and causal
+        return ref.attention_prefill(q, k, v, causal, scale, q_off, window)
+    if (q.shape[1] >= 4096 and q_off == 0 and causal and window == 0
             and q.shape[1] == k.shape[1]):
         # long-context full prefill: ROCm flash SDPA measured faster
         # than the hand-written kernel at S >= 4k (376 vs 259 TF,
@@ -343,14 +350,22 @@ def attention_prefill(q, k, v, causal: bool = True,
         k = k.contiguous()
     if v.stride(-1) != 1:
         v = v.contiguous()
-    return _require_ext().prefill_attn(q.contiguous(), k, v, scale, causal,
-                                       q_off)
+    C = _require_ext()
+    if window > 0:
+        attn_window_dispatch_count += 1
+        return C.prefill_attn(q.contiguous(), k, v, scale, causal, q_off,
+                              window)
+    return C.prefill_attn(q.contiguous(), k, v, scale, causal, q_off)
 
 
 # incremented whenever the carried-state kernel handles a chunk (same
 # purpose as gemm_dispatch_count: a silent fallback to torch math cannot
 # pass as kernel coverage)
 attn_carry_dispatch_count = 0
+
+# the same for the sliding window: calls of the prefill / decode kernels
+# with window > 0
+attn_window_dispatch_count = 0
 
 
 class AttnCarry:
@@ -434,14 +449,33 @@ class _FlashAttnFn(torch.autograd.Function):
 
 
 def attention_train(q, k, v, causal: bool = True,
-                    scale: Optional[float] = None) -> torch.Tensor:
+                    scale: Optional[float] = None,
+                    window: int = 0) -> torch.Tensor:
     """Training attention with autograd. GPU bf16 runs the hand-written
     flash forward+backward kernels; CPU (and unsupported head dims)
-    composes torch SDPA."""
+    composes torch SDPA.
+
+    window > 0 (causal only) is sliding-window attention. The backward
+    kernels have no window, so on every device it composes SDPA with an
+    explicit boolean band mask: correct, but off the HIP path."""
     B, S, Hq, D = q.shape
     Hkv = k.shape[2]
     if scale is None:
         scale = 1.0 / math.sqrt(D)
+    if window > 0:
+        if not causal:
+            raise ValueError("a sliding window requires causal attention")
+        rows = torch.arange(S, device=q.device).unsqueeze(1)
+        rows = rows + (k.shape[1] - S)
+        cols = torch.arange(k.shape[1], device=q.device).unsqueeze(0)
+        band = (cols <= rows) & (cols + window > rows)
+        rep = Hq // Hkv
+        out = torch.nn.functional.scaled_dot_product_attention(
+            q.transpose(1, 2),
+            k.transpose(1, 2).repeat_interleave(rep, dim=1),
+            v.transpose(1, 2).repeat_interleave(rep, dim=1),
+            attn_mask=band, scale=scale)
+        return out.transpose(1, 2)
     if (q.is_cuda and q.dtype == torch.bfloat16 and _C is not None
             and D in (64, 128) and k.shape[1] == S):
         return _FlashAttnFn.apply(q, k, v, causal, scale)
@@ -463,11 +497,16 @@ def attention_train(q, k, v, causal: bool = True,
 def attention_decode(q, k_cache, v_cache, seq_lens,
                      scale: Optional[float] = None, n_split: int = 0,
                      block_table: Optional[torch.Tensor] = None,
-                     len_add: int = 0) -> torch.Tensor:
+                     len_add: int = 0, window: int = 0) -> torch.Tensor:
     """q [B,1,Hq,D] or [B,Hq,D]; caches [B,Hkv,Smax,D] (or paged pools +
     block_table); seq_lens [B]. n_split: flash-decode splits (0 = auto).
     Row b attends to its first seq_lens[b] + len_add keys; len_add is
-    added in-kernel, sparing the caller a per-layer tensor add."""
+    added in-kernel, sparing the caller a per-layer tensor add.
+    window > 0: row b attends to the last `window` of those keys only
+    (sliding window; MFMA kernel only, GQA group <= 16). 0 = no window."""
+    global attn_window_dispatch_count
+    if window < 0:
+        raise ValueError("window must be >= 0")
     squeeze = q.dim() == 4
     if squeeze:
         q3 = q.squeeze(1)
@@ -488,16 +527,23 @@ def attention_decode(q, k_cache, v_cache, seq_lens,
             kc = kc.reshape(B, np_ * 128, *kc.shape[3:])[:, :L]
             vc = vc.reshape(B, np_ * 128, *vc.shape[3:])[:, :L]
             out = ref.attention_decode(q3.unsqueeze(1), kc, vc, seq_lens,
-                                       scale)
+                                       scale, window)
         else:
             out = ref.attention_decode(q3.unsqueeze(1),
                                        k_cache.permute(0, 2, 1, 3),
                                        v_cache.permute(0, 2, 1, 3),
-                                       seq_lens, scale)
+                                       seq_lens, scale, window)
         return out if squeeze else out.squeeze(1)
-    out = _require_ext().decode_attn(
-        q3.contiguous(), k_cache, v_cache, seq_lens.int(), scale, n_split,
-        block_table.int() if block_table is not None else None, len_add)
+    C = _require_ext()
+    bt = block_table.int() if block_table is not None else None
+    if window > 0:
+        out = C.decode_attn(q3.contiguous(), k_cache, v_cache,
+                            seq_lens.int(), scale, n_split, bt, len_add,
+                            window)
+        attn_window_dispatch_count += 1
+    else:
+        out = C.decode_attn(q3.contiguous(), k_cache, v_cache,
+                            seq_lens.int(), scale, n_split, bt, len_add)
     return out.unsqueeze(1) if squeeze else out
 
 

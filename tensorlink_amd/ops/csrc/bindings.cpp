@@ -4,6 +4,8 @@
 
 #include <torch/extension.h>
 
+#include <algorithm>
+#include <climits>
 #include <cstdlib>
 
 #include <c10/hip/HIPStream.h>
@@ -39,7 +41,7 @@ void tl_prefill_attn(const void* q, const void* k, const void* v, void* out,
                      int B, int Sq, int Skv, int q_off, int Hq, int Hkv,
                      int D, float scale, int causal,
                      const int64_t* k_strides, const int64_t* v_strides,
-                     int use_v3, hipStream_t stream);
+                     int use_v3, int window, hipStream_t stream);
 void tl_rope_append(const void* qkv, const void* bias, void* q_out,
                     void* k_cache, void* v_cache, const void* positions,
                     const void* inv_freq, const void* block_table,
@@ -61,7 +63,7 @@ void tl_decode_attn_mfma(const void* q, const void* k_cache,
                          const void* block_table, void* out,
                          void* partial, void* partial_ml, int B, int Hq,
                          int Hkv, int Smax, int D, float scale, int n_split,
-                         int bt_stride, int per_row, int len_add,
+                         int bt_stride, int per_row, int len_add, int window,
                          hipStream_t stream);
 void tl_skinny_gemm(const void* x, const void* w, const void* bias,
                     void* out, void* partial, int M, int N, int K,
@@ -291,7 +293,8 @@ void adamw_(Tensor param, Tensor grad, Tensor m, Tensor v, double lr,
 
 Tensor decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor seq_lens,
                    double scale, int64_t n_split,
-                   c10::optional<Tensor> block_table, int64_t len_add) {
+                   c10::optional<Tensor> block_table, int64_t len_add,
+                   int64_t window) {
   CHECK_IN(q, torch::kBFloat16);
   CHECK_IN(k_cache, torch::kBFloat16);
   CHECK_IN(v_cache, torch::kBFloat16);
@@ -310,10 +313,15 @@ Tensor decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor seq_lens,
   }
   TORCH_CHECK(D == 64 || D == 128, "head_dim must be 64 or 128");
   TORCH_CHECK(Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
+  TORCH_CHECK(window >= 0, "window must be >= 0 (0 = no window)");
   auto out = torch::empty_like(q);
   const bool legacy = (getenv("TL_DECODE_LEGACY") != nullptr || G > 16) &&
                       bt == nullptr;
   if (legacy) {
+    TORCH_CHECK(window == 0,
+                "sliding-window decode runs on the MFMA kernel only (GQA "
+                "group <= 16, TL_DECODE_LEGACY unset); the v1 kernel would "
+                "read the full length");
     tl_decode_attn(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
                    seq_lens.data_ptr(), out.data_ptr(), B, Hq, Hkv, Smax, D,
                    (float)scale, (int)len_add, cur_stream());
@@ -327,7 +335,9 @@ Tensor decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor seq_lens,
     // (cache capacity, which bounds seq_lens + len_add too), no device
     // sync needed.
     per_row = 1;
-    const int upper = bt ? bt_stride * 128 : Smax;
+    // A window caps the keys a row reads, so it caps the bound as well.
+    int upper = bt ? bt_stride * 128 : Smax;
+    if (window > 0) upper = (int)std::min<int64_t>(upper, window);
     n_split = tl_split_for_len(upper);
   }
   TORCH_CHECK(n_split <= 64, "n_split too large");
@@ -344,7 +354,8 @@ Tensor decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor seq_lens,
   tl_decode_attn_mfma(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
                       seq_lens.data_ptr(), bt, out.data_ptr(), pp, pml, B,
                       Hq, Hkv, Smax, D, (float)scale, (int)n_split,
-                      bt_stride, per_row, (int)len_add, cur_stream());
+                      bt_stride, per_row, (int)len_add,
+                      (int)std::min<int64_t>(window, INT_MAX), cur_stream());
   return out;
 }
 
@@ -391,10 +402,15 @@ PrefillKV prefill_kv(const Tensor& k_in, const Tensor& v_in,
   return p;
 }
 
+// window > 0: sliding window of that many keys (the row's own included),
+// causal only, always the v3 kernel (v2 has no window, so TL_NO_PREFILL_V3
+// does not apply). 0 = no window.
 Tensor prefill_attn(Tensor q, Tensor k, Tensor v, double scale, bool causal,
-                    int64_t q_off) {
+                    int64_t q_off, int64_t window) {
   CHECK_IN(q, torch::kBFloat16);
-  auto kv = prefill_kv(k, v);
+  TORCH_CHECK(window >= 0, "window must be >= 0 (0 = no window)");
+  TORCH_CHECK(window == 0 || causal, "a sliding window requires causal");
+  auto kv = prefill_kv(k, v, /*v3_only=*/window > 0);
   const int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
   const int Skv = k.size(1);
   const int Hkv = k.size(2);
@@ -402,11 +418,13 @@ Tensor prefill_attn(Tensor q, Tensor k, Tensor v, double scale, bool causal,
   TORCH_CHECK(k.size(0) == B && k.size(3) == D && Hq % Hkv == 0,
               "k/v do not match q");
   TORCH_CHECK(q_off + Sq <= Skv || !causal, "q_off + Sq must fit Skv");
+  TORCH_CHECK(window == 0 || (q_off >= 0 && Sq >= 1 && Skv >= 1),
+              "windowed prefill needs q_off >= 0 and non-empty q, k/v");
   auto out = torch::empty_like(q);
   tl_prefill_attn(q.data_ptr(), kv.k.data_ptr(), kv.v.data_ptr(),
                   out.data_ptr(), B, Sq, Skv, (int)q_off, Hq, Hkv, D,
                   (float)scale, causal ? 1 : 0, kv.ks, kv.vs, kv.use_v3,
-                  cur_stream());
+                  (int)std::min<int64_t>(window, INT_MAX), cur_stream());
   return out;
 }
 
@@ -1379,8 +1397,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("swiglu_fwd", &swiglu_fwd, "silu(gate)*up");
   mod.def("swiglu_bwd", &swiglu_bwd, "SwiGLU bwd");
   mod.def("adamw_", &adamw_, "fused AdamW step");
-  mod.def("decode_attn", &decode_attn, "GQA decode attention over KV cache");
-  mod.def("prefill_attn", &prefill_attn, "causal GQA prefill attention");
+  mod.def("decode_attn", &decode_attn, "GQA decode attention over KV cache",
+          py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+          py::arg("seq_lens"), py::arg("scale"), py::arg("n_split"),
+          py::arg("block_table"), py::arg("len_add"), py::arg("window") = 0);
+  mod.def("prefill_attn", &prefill_attn,
+          "causal GQA prefill attention (window > 0: sliding window)",
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),
+          py::arg("causal"), py::arg("q_off"), py::arg("window") = 0);
   mod.def("sample_tokens", &sample_tokens,
           "fused penalties/temperature/top-k/top-p sampling, one block/row");
   mod.def("bump_sample_counter", &bump_sample_counter,

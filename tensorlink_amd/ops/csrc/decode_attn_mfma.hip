@@ -41,7 +41,7 @@ __global__ __launch_bounds__(BLOCK) void decode_attn_mfma_kernel(
     float* __restrict__ partial,       // [B, Hq, SPLIT, D]
     float* __restrict__ partial_ml,    // [B, Hq, SPLIT, 2]
     int Hq, int Hkv, int Smax, float scale, int n_split, int bt_stride,
-    int per_row, int len_add) {
+    int per_row, int len_add, int window) {
   constexpr int KCH = D / 32;        // MFMA k-chunks for QK^T
   constexpr int NS = D / 16;         // PV output col tiles
   const int b = blockIdx.x;
@@ -57,12 +57,21 @@ __global__ __launch_bounds__(BLOCK) void decode_attn_mfma_kernel(
   // composition must not change a row's accumulation — exact-greedy
   // guarantee); the launch z-width n_split is a host-side upper bound
   // and surplus blocks exit.
-  const int ns_row = per_row ? tl_split_for_len(L) : n_split;
+  //
+  // window > 0 (sliding window): the row attends to its last min(window, L)
+  // keys, [lo, L). Everything from here on sees that range as a row of
+  // length Lw whose keys start at position lo: the split count, the split
+  // bounds and the tile starts relative to lo are those of an unwindowed
+  // row of length Lw, so the result is bit-identical to the plain kernel
+  // on a cache holding just those keys. window = 0 gives lo = 0, Lw = L.
+  const int lo = window > 0 ? max(0, L - window) : 0;
+  const int Lw = L - lo;
+  const int ns_row = per_row ? tl_split_for_len(Lw) : n_split;
   if (split >= ns_row) return;
 
   // this split's key range
-  const int per_split = (L + ns_row - 1) / ns_row;
-  const int k_begin = split * per_split;
+  const int per_split = (Lw + ns_row - 1) / ns_row;
+  const int k_begin = lo + split * per_split;
   const int k_end = min(L, k_begin + per_split);
 
   const int lane = threadIdx.x & 63;
@@ -266,11 +275,13 @@ template <int D>
 __global__ __launch_bounds__(128) void decode_attn_combine_kernel(
     const float* __restrict__ partial, const float* __restrict__ partial_ml,
     const int* __restrict__ seq_lens, bf16* __restrict__ out, int Hq,
-    int n_split, int per_row, int len_add) {
+    int n_split, int per_row, int len_add, int window) {
   const int bh = blockIdx.x;                    // b * Hq + h
   const int d = threadIdx.x;                    // [0, D)
-  const int ns_row =
-      per_row ? tl_split_for_len(seq_lens[bh / Hq] + len_add) : n_split;
+  // the split count the main kernel derived: from the windowed length
+  int Lw = seq_lens[bh / Hq] + len_add;
+  if (window > 0) Lw = min(Lw, window);
+  const int ns_row = per_row ? tl_split_for_len(Lw) : n_split;
   __shared__ float sm[64], sl[64];
   if (threadIdx.x < ns_row) {
     sm[threadIdx.x] = partial_ml[((int64_t)bh * n_split + threadIdx.x) * 2];
@@ -294,12 +305,13 @@ extern "C" {
 
 // scratch: partial floats [B*Hq*n_split*D] + ml [B*Hq*n_split*2]; pass
 // nullptr when n_split == 1.
+// window > 0: each row attends to its last min(window, L) keys only.
 void tl_decode_attn_mfma(const void* q, const void* k_cache,
                          const void* v_cache, const void* seq_lens,
                          const void* block_table, void* out,
                          void* partial, void* partial_ml, int B, int Hq,
                          int Hkv, int Smax, int D, float scale, int n_split,
-                         int bt_stride, int per_row, int len_add,
+                         int bt_stride, int per_row, int len_add, int window,
                          hipStream_t stream) {
   dim3 grid(B, Hkv, n_split), block(BLOCK);
 #define LAUNCH(DD, SM, PG)                                                   \
@@ -308,7 +320,7 @@ void tl_decode_attn_mfma(const void* q, const void* k_cache,
                      (const bf16*)v_cache, (const int*)seq_lens,             \
                      (const int*)block_table, (bf16*)out,                    \
                      (float*)partial, (float*)partial_ml, Hq, Hkv, Smax,     \
-                     scale, n_split, bt_stride, per_row, len_add)
+                     scale, n_split, bt_stride, per_row, len_add, window)
 #define PICK(DD)                                                             \
   do {                                                                       \
     if (block_table) {                                                       \
@@ -327,12 +339,14 @@ void tl_decode_attn_mfma(const void* q, const void* k_cache,
       hipLaunchKernelGGL((decode_attn_combine_kernel<128>), cgrid, cblock, 0,
                          stream, (const float*)partial,
                          (const float*)partial_ml, (const int*)seq_lens,
-                         (bf16*)out, Hq, n_split, per_row, len_add);
+                         (bf16*)out, Hq, n_split, per_row, len_add,
+                         window);
     else
       hipLaunchKernelGGL((decode_attn_combine_kernel<64>), cgrid, cblock, 0,
                          stream, (const float*)partial,
                          (const float*)partial_ml, (const int*)seq_lens,
-                         (bf16*)out, Hq, n_split, per_row, len_add);
+                         (bf16*)out, Hq, n_split, per_row, len_add,
+                         window);
   }
 }
 

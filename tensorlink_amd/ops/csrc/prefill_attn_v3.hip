@@ -25,6 +25,10 @@
 // q_off + the end of its 64-row half), so even the sign of a zero matches.
 //
 // LDS: 2 x (K 17,408 + V 16,640) + P 9,216 = 77,312 B -> 2 blocks per CU.
+//
+// WIN = 1 is the sliding-window variant (see the kernel's comment): key
+// tiles wholly left of the band are never staged, and the tiles the band's
+// left edge crosses take the two-sided mask.
 
 #include "common.hpp"
 
@@ -73,11 +77,14 @@ DEVINLINE void ds_read_tr16_frag4(unsigned addr_bytes, bf16x8_t (&f)[4]) {
 // expressions in v2's order. s = raw QK^T accumulators in, P written to
 // pw[16][BN + PPAD] as bf16. MASK = false only for tiles wholly below the
 // diagonal and below Skv, where v2's select always takes the product.
-template <bool MASK, bool PIN_FMA>
+// WIN adds the band's left edge to the mask: key j is hidden from row p
+// when j + window <= p.
+template <bool MASK, bool PIN_FMA, bool WIN>
 DEVINLINE void softmax_frag(f32x4 (&s)[4], float (&m_run)[4],
                             float (&l_run)[4], float (&alpha)[4], int kt0,
                             int qrow0, int Skv, int causal, float scale,
-                            bf16 (*pw)[BN + PPAD], int col, int quad) {
+                            bf16 (*pw)[BN + PPAD], int col, int quad,
+                            int window) {
   float row_max[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) row_max[r] = -1e30f;
@@ -88,7 +95,8 @@ DEVINLINE void softmax_frag(f32x4 (&s)[4], float (&m_run)[4],
     for (int r = 0; r < 4; ++r) {
       if constexpr (MASK) {
         const int qrow = qrow0 + quad * 4 + r;
-        const bool masked = (kcol >= Skv) || (causal && kcol > qrow);
+        bool masked = (kcol >= Skv) || (causal && kcol > qrow);
+        if constexpr (WIN) masked = masked || (kcol + window <= qrow);
         s[ns][r] = masked ? -1e30f : s[ns][r] * scale;
       } else {
         float sv = s[ns][r] * scale;
@@ -130,9 +138,10 @@ DEVINLINE void softmax_frag(f32x4 (&s)[4], float (&m_run)[4],
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     // the plain kernel's compile contracts this to one fma (as v2's does);
-    // the carried variant's does so for some rows only, so there the fma
-    // is spelled out. Spelling it out for both moves the plain kernel's
-    // register allocation, which stays as it was measured.
+    // the carried variant's does so for some rows only, so there (and in
+    // the windowed variant) the fma is spelled out. Spelling it out for
+    // all moves the plain kernel's register allocation, which stays as it
+    // was measured.
     if constexpr (PIN_FMA)
       l_run[r] = __builtin_fmaf(l_run[r], alpha[r], psum[r]);
     else
@@ -156,8 +165,29 @@ DEVINLINE void softmax_frag(f32x4 (&s)[4], float (&m_run)[4],
 // between prologue and epilogue is the same code for both variants; with
 // chunk boundaries on multiples of BN and chunks in ascending order the
 // carried calls run v3's tile steps in v3's order (bit-identical result).
-// CARRY = 0 ignores the four trailing arguments.
-template <int D, int CARRY>
+// CARRY = 0 ignores the four arguments after v_ss.
+//
+// WIN = 1 is the sliding-window variant (causal only, CARRY = 0 only): the
+// query at global position p sees key j iff p - window < j <= p. A window
+// is work removed. Key tiles stay aligned to absolute multiples of BN; the
+// block's first staged tile is the one holding the left edge of its lowest
+// row, a wave starts at the tile holding the left edge of the first row of
+// its 64-row half (the half rule that sets its last tile), and tiles the
+// left edge of any of the wave's 32 rows crosses take the MASK = true path
+// with the second compare. Staging, the double buffer, the one barrier per
+// tile and the clamp-to-Skv-1 addressing are the plain kernel's.
+//
+// Where a wave starts does not reach the bits. A tile wholly masked for a
+// row is an exact no-op on that row's state: row_max = -1e30 <= m_run so
+// m_new = m_run and alpha = __expf(0) = 1; every p = 0 through the
+// s <= -1e29f select; l = l * 1 + 0 and oacc = oacc * 1 + 0 * v. Masked
+// entries of a partly visible tile add exact zeros the same way. So a row's
+// output is a function of its global position, the window and the keys in
+// absolute 64-key tiles ascending, and of nothing else: not q0, not the
+// wave, not q_off, not how the prompt was chunked. Chunked prefill of a
+// windowed model is bit-identical to the one-shot prefill.
+// WIN = 0 does not read `window`.
+template <int D, int CARRY, int WIN>
 __global__ __launch_bounds__(BLOCK)
 __attribute__((amdgpu_waves_per_eu(2))) void prefill_attn_v3_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k,
@@ -165,8 +195,9 @@ __attribute__((amdgpu_waves_per_eu(2))) void prefill_attn_v3_kernel(
     float* __restrict__ lse, int B, int Sq, int Skv, int q_off, int Hq,
     int Hkv, float scale, int causal, int64_t k_sb, int64_t k_sh,
     int64_t k_ss, int64_t v_sb, int64_t v_sh, int64_t v_ss, float* o_state,
-    float* ml_state, int first, int last) {
+    float* ml_state, int first, int last, int window) {
   static_assert(D == 64 || D == 128);
+  static_assert(!(CARRY && WIN), "the carried kernel has no window");
   constexpr int KCH = D / 32;      // QK^T k-chunks
   constexpr int NSUB = BN / 16;    // score col tiles = 4
   constexpr int NS_PV = D / 16;    // PV output col tiles
@@ -249,6 +280,14 @@ __attribute__((amdgpu_waves_per_eu(2))) void prefill_attn_v3_kernel(
   const int half0 = q0 + (wave >> 1) * HALF;
   const int kv_end_w = causal ? min(Skv, q_off + half0 + HALF) : Skv;
   const int my_tiles = half0 < Sq ? (kv_end_w + BN - 1) / BN : 0;
+  // WIN: first tile of the block (lowest row's left edge) and of the wave
+  // (its half's first row's left edge); both < n_tiles since the row's own
+  // position is a visible key
+  int t_lo_blk = 0, t_lo_w = 0;
+  if constexpr (WIN) {
+    t_lo_blk = max(0, q_off + q0 - window + 1) / BN;
+    t_lo_w = max(0, q_off + half0 - window + 1) / BN;
+  }
 
   const bf16* kb = k + (int64_t)b * k_sb + (int64_t)hkv * k_sh;
   const bf16* vb = v + (int64_t)b * v_sb + (int64_t)hkv * v_sh;
@@ -288,17 +327,22 @@ __attribute__((amdgpu_waves_per_eu(2))) void prefill_attn_v3_kernel(
     }
   };
 
-  stage_load(0);
-  stage_store(0, 0);
+  if constexpr (WIN) {
+    stage_load(t_lo_blk * BN);
+    stage_store(t_lo_blk * BN, t_lo_blk & 1);
+  } else {
+    stage_load(0);
+    stage_store(0, 0);
+  }
   __syncthreads();
 
-  for (int t = 0; t < n_tiles; ++t) {
+  for (int t = WIN ? t_lo_blk : 0; t < n_tiles; ++t) {
     const int kt0 = t * BN;
     const int cur = t & 1;
     const bool more = t + 1 < n_tiles;
     if (more) stage_load(kt0 + BN);
 
-    if (t < my_tiles) {
+    if (t < my_tiles && (!WIN || t >= t_lo_w)) {
       // ---- QK^T: each K fragment feeds both row fragments ----
       f32x4 sacc[2][NSUB];
 #pragma unroll
@@ -320,22 +364,25 @@ __attribute__((amdgpu_waves_per_eu(2))) void prefill_attn_v3_kernel(
       // the mask compare only where the tile crosses Skv or the wave's
       // first row's diagonal (wave-uniform: EXEC stays full for the
       // transposed reads)
-      const bool need_mask =
+      bool need_mask =
           (kt0 + BN > Skv) || (causal && kt0 + BN - 1 > q_off + q0 + r0);
+      // ... or the left edge of any of the wave's 32 rows
+      if constexpr (WIN)
+        need_mask = need_mask || (kt0 + window <= q_off + q0 + r0 + 31);
       float alpha[2][4];
       bf16x8_t pa[2][BN / 32];
 #pragma unroll
       for (int f = 0; f < 2; ++f) {
         if (need_mask)
-          softmax_frag<true, CARRY != 0>(
+          softmax_frag<true, (CARRY | WIN) != 0, WIN != 0>(
               sacc[f], m_run[f], l_run[f], alpha[f], kt0,
               q_off + q0 + r0 + f * 16, Skv, causal, scale, p_lds[wave], col,
-              quad);
+              quad, WIN ? window : 0);
         else
-          softmax_frag<false, CARRY != 0>(
+          softmax_frag<false, (CARRY | WIN) != 0, false>(
               sacc[f], m_run[f], l_run[f], alpha[f], kt0,
               q_off + q0 + r0 + f * 16, Skv, causal, scale, p_lds[wave], col,
-              quad);
+              quad, 0);
 #pragma unroll
         for (int ks = 0; ks < BN / 32; ++ks)
           pa[f][ks] = *reinterpret_cast<const bf16x8_t*>(
@@ -428,17 +475,43 @@ extern "C" void tl_prefill_attn_v3(
     int64_t v_sh, int64_t v_ss, hipStream_t stream) {
   dim3 grid((Sq + BM - 1) / BM, Hq, B), block(BLOCK);
   if (D == 128)
-    hipLaunchKernelGGL((prefill_attn_v3_kernel<128, 0>), grid, block, 0,
+    hipLaunchKernelGGL((prefill_attn_v3_kernel<128, 0, 0>), grid, block, 0,
                        stream, (const bf16*)q, (const bf16*)k,
                        (const bf16*)v, (bf16*)out, (float*)lse, B, Sq, Skv,
                        q_off, Hq, Hkv, scale, causal, k_sb, k_sh, k_ss, v_sb,
-                       v_sh, v_ss, (float*)nullptr, (float*)nullptr, 1, 1);
+                       v_sh, v_ss, (float*)nullptr, (float*)nullptr, 1, 1, 0);
   else if (D == 64)
-    hipLaunchKernelGGL((prefill_attn_v3_kernel<64, 0>), grid, block, 0,
+    hipLaunchKernelGGL((prefill_attn_v3_kernel<64, 0, 0>), grid, block, 0,
                        stream, (const bf16*)q, (const bf16*)k,
                        (const bf16*)v, (bf16*)out, (float*)lse, B, Sq, Skv,
                        q_off, Hq, Hkv, scale, causal, k_sb, k_sh, k_ss, v_sb,
-                       v_sh, v_ss, (float*)nullptr, (float*)nullptr, 1, 1);
+                       v_sh, v_ss, (float*)nullptr, (float*)nullptr, 1, 1, 0);
+}
+
+// Sliding-window entry: causal, window >= 1 (see the kernel's comment). A
+// window past Skv hides nothing, so it is clamped there and the kernel's
+// `key + window` never overflows.
+extern "C" void tl_prefill_attn_win(
+    const void* q, const void* k, const void* v, void* out, int B, int Sq,
+    int Skv, int q_off, int Hq, int Hkv, int D, float scale, int window,
+    int64_t k_sb, int64_t k_sh, int64_t k_ss, int64_t v_sb, int64_t v_sh,
+    int64_t v_ss, hipStream_t stream) {
+  dim3 grid((Sq + BM - 1) / BM, Hq, B), block(BLOCK);
+  window = max(1, min(window, Skv));
+  if (D == 128)
+    hipLaunchKernelGGL((prefill_attn_v3_kernel<128, 0, 1>), grid, block, 0,
+                       stream, (const bf16*)q, (const bf16*)k,
+                       (const bf16*)v, (bf16*)out, (float*)nullptr, B, Sq,
+                       Skv, q_off, Hq, Hkv, scale, 1, k_sb, k_sh, k_ss, v_sb,
+                       v_sh, v_ss, (float*)nullptr, (float*)nullptr, 1, 1,
+                       window);
+  else if (D == 64)
+    hipLaunchKernelGGL((prefill_attn_v3_kernel<64, 0, 1>), grid, block, 0,
+                       stream, (const bf16*)q, (const bf16*)k,
+                       (const bf16*)v, (bf16*)out, (float*)nullptr, B, Sq,
+                       Skv, q_off, Hq, Hkv, scale, 1, k_sb, k_sh, k_ss, v_sb,
+                       v_sh, v_ss, (float*)nullptr, (float*)nullptr, 1, 1,
+                       window);
 }
 
 // Carried-state entry: one key chunk of a longer softmax per call (see the
@@ -452,17 +525,17 @@ extern "C" void tl_prefill_attn_carry(
     int64_t v_ss, hipStream_t stream) {
   dim3 grid((Sq + BM - 1) / BM, Hq, B), block(BLOCK);
   if (D == 128)
-    hipLaunchKernelGGL((prefill_attn_v3_kernel<128, 1>), grid, block, 0,
+    hipLaunchKernelGGL((prefill_attn_v3_kernel<128, 1, 0>), grid, block, 0,
                        stream, (const bf16*)q, (const bf16*)k,
                        (const bf16*)v, (bf16*)out, (float*)lse, B, Sq, Skv,
                        q_off, Hq, Hkv, scale, causal, k_sb, k_sh, k_ss, v_sb,
                        v_sh, v_ss, (float*)o_state, (float*)ml_state, first,
-                       last);
+                       last, 0);
   else if (D == 64)
-    hipLaunchKernelGGL((prefill_attn_v3_kernel<64, 1>), grid, block, 0,
+    hipLaunchKernelGGL((prefill_attn_v3_kernel<64, 1, 0>), grid, block, 0,
                        stream, (const bf16*)q, (const bf16*)k,
                        (const bf16*)v, (bf16*)out, (float*)lse, B, Sq, Skv,
                        q_off, Hq, Hkv, scale, causal, k_sb, k_sh, k_ss, v_sb,
                        v_sh, v_ss, (float*)o_state, (float*)ml_state, first,
-                       last);
+                       last, 0);
 }

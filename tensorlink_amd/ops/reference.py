@@ -92,10 +92,14 @@ def swiglu(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
 # --------------------------------------------------------------------------
 def attention_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                       causal: bool = True, scale: Optional[float] = None,
-                      q_off: int = 0) -> torch.Tensor:
+                      q_off: int = 0, window: int = 0) -> torch.Tensor:
     """Causal GQA attention. q [B,Sq,Hq,D], k/v [B,Skv,Hkv,D] →
     [B,Sq,Hq,D]. q_off: query row i sits at global position q_off+i
-    (chunked prefill against Skv = q_off + Sq history+chunk keys)."""
+    (chunked prefill against Skv = q_off + Sq history+chunk keys).
+    window > 0 (causal only): the row at position p sees key j iff
+    p - window < j <= p, i.e. `window` keys with its own; 0 = no window."""
+    if window and not causal:
+        raise ValueError("a sliding window requires causal attention")
     B, Sq, Hq, D = q.shape
     Skv = k.shape[1]
     Hkv = k.shape[2]
@@ -109,6 +113,8 @@ def attention_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         rows = torch.arange(Sq, device=q.device).unsqueeze(1) + q_off
         cols = torch.arange(Skv, device=q.device).unsqueeze(0)
         scores = scores.masked_fill(cols > rows, float("-inf"))
+        if window > 0:
+            scores = scores.masked_fill(cols + window <= rows, float("-inf"))
     p = scores.softmax(-1)
     out = torch.matmul(p, vf)
     return out.transpose(1, 2).to(q.dtype)
@@ -166,11 +172,13 @@ def attention_prefill_carry(q: torch.Tensor, k: torch.Tensor,
 
 def attention_decode(q: torch.Tensor, k_cache: torch.Tensor,
                      v_cache: torch.Tensor, seq_lens: torch.Tensor,
-                     scale: Optional[float] = None) -> torch.Tensor:
+                     scale: Optional[float] = None,
+                     window: int = 0) -> torch.Tensor:
     """Single-token decode over a contiguous KV cache.
 
     q [B,1,Hq,D]; k_cache/v_cache [B,Smax,Hkv,D]; seq_lens [B] = valid kv
     length per sequence (incl. the current token already written).
+    window > 0: only the last `window` of those keys, [max(0, L - window), L).
     """
     B, _, Hq, D = q.shape
     Hkv = k_cache.shape[2]
@@ -179,8 +187,9 @@ def attention_decode(q: torch.Tensor, k_cache: torch.Tensor,
     out = torch.empty_like(q)
     for b in range(B):
         L = int(seq_lens[b])
-        kf = k_cache[b, :L].float().repeat_interleave(rep, dim=1)   # [L,Hq,D]
-        vf = v_cache[b, :L].float().repeat_interleave(rep, dim=1)
+        lo = max(0, L - window) if window > 0 else 0
+        kf = k_cache[b, lo:L].float().repeat_interleave(rep, dim=1)  # [L,Hq,D]
+        vf = v_cache[b, lo:L].float().repeat_interleave(rep, dim=1)
         qf = q[b, 0].float()                                        # [Hq,D]
         scores = torch.einsum("hd,lhd->hl", qf, kf) * scale
         p = scores.softmax(-1)

@@ -118,6 +118,15 @@ def _ring_accumulate(q, scale, rank, steps):
     return o / l.permute(0, 2, 1).unsqueeze(-1).clamp(min=1e-30)
 
 
+def _reject_window(config: ModelConfig) -> None:
+    # ring attention runs the carried-state kernel, which has no window:
+    # a windowed model would silently attend to the full sequence
+    if config.sliding_window:
+        raise NotImplementedError(
+            f"context parallelism has no sliding-window attention "
+            f"({config.name}: sliding_window={config.sliding_window})")
+
+
 class CPRunner:
     """Sequence-sharded prefill across a CP group (weights replicated,
     same seeded init on every rank)."""
@@ -130,6 +139,7 @@ class CPRunner:
                  else torch.float32)
         config = (model if isinstance(model, ModelConfig)
                   else get_config(model))
+        _reject_window(config)
         self.stage = build_full_model(config)
         init_random_stage(self.stage, device=self.device, dtype=dtype,
                           seed=seed)
@@ -364,6 +374,7 @@ class CPTrainer:
                       else torch.float32)
         config = (model if isinstance(model, ModelConfig)
                   else get_config(model))
+        _reject_window(config)
         self.stage = build_full_model(config)
         init_random_stage(self.stage, device=self.device, dtype=self.dtype,
                           seed=seed)
