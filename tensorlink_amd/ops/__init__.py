@@ -424,16 +424,19 @@ class _FlashAttnFn(torch.autograd.Function):
     """Hand-written flash attention for training (gfx950): forward =
     prefill kernel saving the logsumexp; backward = the two MFMA kernels
     in ops/csrc/flash_bwd.hip (dKV over key tiles, dQ over query tiles)
-    with Delta = rowsum(dO*O) precomputed in fp32."""
+    with Delta = rowsum(dO*O) precomputed in fp32. window > 0 runs the
+    windowed instantiations of all three kernels on the [B,S,Hkv,D] k/v
+    as they are: no band mask tensor, no repeated heads."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, scale):
+    def forward(ctx, q, k, v, causal, scale, window=0):
         C = _require_ext()
         out, lse = C.prefill_attn_lse(q.contiguous(), k.contiguous(),
-                                      v.contiguous(), scale, causal)
+                                      v.contiguous(), scale, causal, window)
         ctx.save_for_backward(q, k, v, out, lse)
         ctx.causal = causal
         ctx.scale = scale
+        ctx.window = window
         return out
 
     @staticmethod
@@ -444,8 +447,8 @@ class _FlashAttnFn(torch.autograd.Function):
         delta = delta.permute(0, 2, 1).contiguous()           # [B,Hq,S]
         dq, dk, dv = C.attn_bwd(q.contiguous(), k.contiguous(),
                                 v.contiguous(), dout.contiguous(), lse,
-                                delta, ctx.scale, ctx.causal)
-        return dq, dk, dv, None, None
+                                delta, ctx.scale, ctx.causal, ctx.window)
+        return dq, dk, dv, None, None, None
 
 
 def attention_train(q, k, v, causal: bool = True,
@@ -455,9 +458,14 @@ def attention_train(q, k, v, causal: bool = True,
     flash forward+backward kernels; CPU (and unsupported head dims)
     composes torch SDPA.
 
-    window > 0 (causal only) is sliding-window attention. The backward
-    kernels have no window, so on every device it composes SDPA with an
-    explicit boolean band mask: correct, but off the HIP path."""
+    window > 0 (causal only) is sliding-window attention: the query at
+    position p sees key j iff p - window < j <= p. GPU bf16 at head dim
+    64 / 128 with Sq == Skv runs the windowed instantiations of the same
+    kernels, forward and backward, at every length; everything else
+    composes SDPA with an explicit boolean band mask. TL_NO_SWA_TRAIN=1
+    (read per call) keeps that composition on the GPU too, for A/B runs
+    and tests."""
+    global attn_window_dispatch_count
     B, S, Hq, D = q.shape
     Hkv = k.shape[2]
     if scale is None:
@@ -465,6 +473,11 @@ def attention_train(q, k, v, causal: bool = True,
     if window > 0:
         if not causal:
             raise ValueError("a sliding window requires causal attention")
+        if (q.is_cuda and q.dtype == torch.bfloat16 and _C is not None
+                and D in (64, 128) and k.shape[1] == S
+                and not _os.environ.get("TL_NO_SWA_TRAIN")):
+            attn_window_dispatch_count += 1
+            return _FlashAttnFn.apply(q, k, v, True, scale, window)
         rows = torch.arange(S, device=q.device).unsqueeze(1)
         rows = rows + (k.shape[1] - S)
         cols = torch.arange(k.shape[1], device=q.device).unsqueeze(0)

@@ -121,6 +121,12 @@ void tl_prefill_attn_lse(const void* q, const void* k, const void* v,
                          int causal, const int64_t* k_strides,
                          const int64_t* v_strides, int use_v3,
                          hipStream_t stream);
+void tl_prefill_attn_win(const void* q, const void* k, const void* v,
+                         void* out, void* lse, int B, int Sq, int Skv,
+                         int q_off, int Hq, int Hkv, int D, float scale,
+                         int window, int64_t k_sb, int64_t k_sh, int64_t k_ss,
+                         int64_t v_sb, int64_t v_sh, int64_t v_ss,
+                         hipStream_t stream);
 void tl_prefill_attn_carry(const void* q, const void* k, const void* v,
                            void* out, void* lse, void* o_state,
                            void* ml_state, int B, int Sq, int Skv, int q_off,
@@ -131,7 +137,7 @@ void tl_prefill_attn_carry(const void* q, const void* k, const void* v,
 void tl_attn_bwd(const void* q, const void* k, const void* v,
                  const void* dout, const void* lse, const void* delta,
                  void* dq, void* dk, void* dv, int B, int S, int Hq,
-                 int Hkv, int D, float scale, int causal,
+                 int Hkv, int D, float scale, int causal, int window,
                  hipStream_t stream);
 }
 
@@ -428,10 +434,16 @@ Tensor prefill_attn(Tensor q, Tensor k, Tensor v, double scale, bool causal,
   return out;
 }
 
+// window > 0: the forward of windowed training (flash_bwd.hip's WIN kernels
+// take the lse). Causal only, the v3 WIN kernel at every length, as in
+// prefill_attn. 0 = no window.
 std::vector<Tensor> prefill_attn_lse(Tensor q, Tensor k, Tensor v,
-                                     double scale, bool causal) {
+                                     double scale, bool causal,
+                                     int64_t window) {
   CHECK_IN(q, torch::kBFloat16);
-  auto kv = prefill_kv(k, v);
+  TORCH_CHECK(window >= 0, "window must be >= 0 (0 = no window)");
+  TORCH_CHECK(window == 0 || causal, "a sliding window requires causal");
+  auto kv = prefill_kv(k, v, /*v3_only=*/window > 0);
   const int B = q.size(0), Sq = q.size(1), Hq = q.size(2), D = q.size(3);
   const int Skv = k.size(1);
   const int Hkv = k.size(2);
@@ -440,6 +452,17 @@ std::vector<Tensor> prefill_attn_lse(Tensor q, Tensor k, Tensor v,
               "k/v do not match q");
   auto out = torch::empty_like(q);
   auto lse = torch::empty({B, Hq, Sq}, q.options().dtype(torch::kFloat));
+  if (window > 0) {
+    TORCH_CHECK(Sq >= 1 && Sq <= Skv,
+                "windowed prefill needs non-empty q and Sq <= Skv");
+    tl_prefill_attn_win(q.data_ptr(), kv.k.data_ptr(), kv.v.data_ptr(),
+                        out.data_ptr(), lse.data_ptr(), B, Sq, Skv, 0, Hq,
+                        Hkv, D, (float)scale,
+                        (int)std::min<int64_t>(window, INT_MAX), kv.ks[0],
+                        kv.ks[1], kv.ks[2], kv.vs[0], kv.vs[1], kv.vs[2],
+                        cur_stream());
+    return {out, lse};
+  }
   tl_prefill_attn_lse(q.data_ptr(), kv.k.data_ptr(), kv.v.data_ptr(),
                       out.data_ptr(), lse.data_ptr(), B, Sq, Skv, 0, Hq,
                       Hkv, D, (float)scale, causal ? 1 : 0, kv.ks, kv.vs,
@@ -498,7 +521,7 @@ py::object prefill_attn_carry(Tensor q, Tensor k, Tensor v, Tensor o_state,
 
 std::vector<Tensor> attn_bwd(Tensor q, Tensor k, Tensor v, Tensor dout,
                              Tensor lse, Tensor delta, double scale,
-                             bool causal) {
+                             bool causal, int64_t window) {
   CHECK_IN(q, torch::kBFloat16);
   CHECK_IN(k, torch::kBFloat16);
   CHECK_IN(v, torch::kBFloat16);
@@ -509,13 +532,16 @@ std::vector<Tensor> attn_bwd(Tensor q, Tensor k, Tensor v, Tensor dout,
   const int Hkv = k.size(2);
   TORCH_CHECK(k.size(1) == S, "training attention needs Sq == Skv");
   TORCH_CHECK(D == 64 || D == 128, "head_dim must be 64 or 128");
+  TORCH_CHECK(window >= 0, "window must be >= 0 (0 = no window)");
+  TORCH_CHECK(window == 0 || causal, "a sliding window requires causal");
   auto dq = torch::empty_like(q);
   auto dk = torch::empty_like(k);
   auto dv = torch::empty_like(v);
   tl_attn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), dout.data_ptr(),
               lse.data_ptr(), delta.data_ptr(), dq.data_ptr(),
               dk.data_ptr(), dv.data_ptr(), B, S, Hq, Hkv, D, (float)scale,
-              causal ? 1 : 0, cur_stream());
+              causal ? 1 : 0, (int)std::min<int64_t>(window, INT_MAX),
+              cur_stream());
   return {dq, dk, dv};
 }
 
@@ -1433,7 +1459,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("mxfp4_moe_n_split", &mxfp4_moe_n_split_py,
           "split-K count of mxfp4_moe_gemm for (N, K, E)");
   mod.def("prefill_attn_lse", &prefill_attn_lse,
-          "causal GQA prefill attention returning (out, logsumexp)");
+          "causal GQA prefill attention returning (out, logsumexp)",
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),
+          py::arg("causal"), py::arg("window") = 0);
   mod.def("prefill_attn_carry", &prefill_attn_carry,
           "prefill attention over one key chunk with carried (o, m, l) state",
           py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o_state"),
@@ -1441,5 +1469,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("q_off"), py::arg("first"), py::arg("last"),
           py::arg("want_lse") = false);
   mod.def("attn_bwd", &attn_bwd,
-          "flash-attention backward: (dq, dk, dv) from saved lse/delta");
+          "flash-attention backward: (dq, dk, dv) from saved lse/delta "
+          "(window > 0: sliding window)",
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("dout"),
+          py::arg("lse"), py::arg("delta"), py::arg("scale"),
+          py::arg("causal"), py::arg("window") = 0);
 }

@@ -21,6 +21,21 @@
 //
 // Delta[b,h,i] = rowsum(dO_i * O_i) is precomputed (torch, f32).
 // All accumulation in f32; inputs/outputs bf16 except lse/delta f32.
+//
+// WIN = 1 (both kernels) is the sliding-window variant, causal only: the
+// query at position p sees key j iff p - window < j <= p. A window is work
+// removed. Tiles stay aligned to absolute multiples of 64 and only the
+// tiles the band touches are staged:
+//   dKV: q tiles  k0/64 .. min(last, (k0 + 63 + window - 1)/64)
+//   dQ:  key tiles max(0, q0 - window + 1)/64 .. q0/64
+// The mask gains the left edge (key + window <= q). A wave whose 16 keys
+// (dKV) or 16 rows (dQ) see all 64 opposite positions of a tile skips the
+// compares (wave-uniform branch, EXEC stays full).
+//
+// A masked entry is an exact zero (p = 0, so ds = 0, so bf16 0 enters the
+// MFMA), and the tiles run in the plain kernels' order, so where a block
+// starts does not reach the bits: window >= S gives the plain kernels' dq,
+// dk, dv bit for bit. WIN = 0 does not read `window`.
 
 #include "common.hpp"
 
@@ -57,13 +72,13 @@ DEVINLINE void stage_tile(const bf16* __restrict__ src, int64_t base,
 }
 
 // ------------------------------ dK / dV ------------------------------
-template <int D>
+template <int D, int WIN>
 __global__ __launch_bounds__(BLOCK) void attn_bwd_dkv_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k,
     const bf16* __restrict__ v, const bf16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
     bf16* __restrict__ dk, bf16* __restrict__ dv, int B, int S, int Hq,
-    int Hkv, float scale, int causal) {
+    int Hkv, float scale, int causal, int window) {
   constexpr int KCH = D / 32;
   constexpr int ND = D / 16;
   const int kt = blockIdx.x;
@@ -115,11 +130,23 @@ __global__ __launch_bounds__(BLOCK) void attn_bwd_dkv_kernel(
   }
 
   const int qt_start = causal ? (k0 / BT) : 0;
+  // WIN: one past the q tile holding the last row that sees this block's
+  // last key (row k0 + 63 + window - 1), or S's last tile
+  int qt_end = 0;
+  if constexpr (WIN)
+    qt_end = min((S - 1) / BT, (k0 + BT - 1 + window - 1) / BT) + 1;
   for (int g = 0; g < G; ++g) {
     const int h = hkv * G + g;
     const int64_t qbase = ((int64_t)b * S) * Hq * D + (int64_t)h * D;
-    for (int qt = qt_start; qt * BT < S; ++qt) {
+    for (int qt = qt_start; WIN ? qt < qt_end : qt * BT < S; ++qt) {
       const int q0 = qt * BT;
+      // WIN: no compare where all 64 rows exist and see all of the wave's
+      // 16 keys: its last key <= the first row, its first key inside the
+      // last row's window
+      bool need_mask = true;
+      if constexpr (WIN)
+        need_mask = q0 + BT > S || k0 + wave * 16 + 15 > q0 ||
+                    k0 + wave * 16 + window <= q0 + BT - 1;
       // ---- stage Q and dO (rows + panels), L and Delta ----
       stage_tile<D, true, true>(q, qbase, (int64_t)Hq * D, q0, S, q_lds,
                                 q_pan);
@@ -153,15 +180,38 @@ __global__ __launch_bounds__(BLOCK) void attn_bwd_dkv_kernel(
         const int qcol = q0 + qs * 16 + col;
         const float L = ld_lds[0][qs * 16 + col];
         const float Dl = ld_lds[1][qs * 16 + col];
+        if constexpr (WIN) {
+          if (need_mask) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int key = k0 + wave * 16 + quad * 4 + r;
-          const bool masked = (qcol >= S) || key >= S ||
-                              (causal && key > qcol) || L <= -1e29f;
-          const float p = masked ? 0.f : __expf(st[r] * scale - L);
-          const float ds = p * (dpt[r] - Dl) * scale;
-          p_lds[wave][quad * 4 + r][qs * 16 + col] = f2bf(p);
-          s_lds[wave][quad * 4 + r][qs * 16 + col] = f2bf(ds);
+            for (int r = 0; r < 4; ++r) {
+              const int key = k0 + wave * 16 + quad * 4 + r;
+              const bool masked = (qcol >= S) || key >= S || key > qcol ||
+                                  key + window <= qcol || L <= -1e29f;
+              const float p = masked ? 0.f : __expf(st[r] * scale - L);
+              const float ds = p * (dpt[r] - Dl) * scale;
+              p_lds[wave][quad * 4 + r][qs * 16 + col] = f2bf(p);
+              s_lds[wave][quad * 4 + r][qs * 16 + col] = f2bf(ds);
+            }
+          } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const float p = __expf(st[r] * scale - L);
+              const float ds = p * (dpt[r] - Dl) * scale;
+              p_lds[wave][quad * 4 + r][qs * 16 + col] = f2bf(p);
+              s_lds[wave][quad * 4 + r][qs * 16 + col] = f2bf(ds);
+            }
+          }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int key = k0 + wave * 16 + quad * 4 + r;
+            const bool masked = (qcol >= S) || key >= S ||
+                                (causal && key > qcol) || L <= -1e29f;
+            const float p = masked ? 0.f : __expf(st[r] * scale - L);
+            const float ds = p * (dpt[r] - Dl) * scale;
+            p_lds[wave][quad * 4 + r][qs * 16 + col] = f2bf(p);
+            s_lds[wave][quad * 4 + r][qs * 16 + col] = f2bf(ds);
+          }
         }
         // ---- contractions run per 32-q chunk (mfma K=32), i.e. after
         // each odd subtile; same-wave ds_write -> ds_read ordering is
@@ -211,13 +261,13 @@ __global__ __launch_bounds__(BLOCK) void attn_bwd_dkv_kernel(
 }
 
 // -------------------------------- dQ ---------------------------------
-template <int D>
+template <int D, int WIN>
 __global__ __launch_bounds__(BLOCK) void attn_bwd_dq_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k,
     const bf16* __restrict__ v, const bf16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
     bf16* __restrict__ dq, int B, int S, int Hq, int Hkv, float scale,
-    int causal) {
+    int causal, int window) {
   constexpr int KCH = D / 32;
   constexpr int ND = D / 16;
   const int qt = blockIdx.x;
@@ -260,7 +310,18 @@ __global__ __launch_bounds__(BLOCK) void attn_bwd_dq_kernel(
 
   const int kv_end = causal ? min(S, q0 + BT) : S;
   const int64_t kbase = ((int64_t)b * S) * Hkv * D + (int64_t)hkv * D;
-  for (int kt0 = 0; kt0 < kv_end; kt0 += BT) {
+  // WIN: start at the tile holding the left edge of the block's first row
+  int kt_lo = 0;
+  if constexpr (WIN) kt_lo = max(0, q0 - window + 1) / BT * BT;
+  for (int kt0 = WIN ? kt_lo : 0; kt0 < kv_end; kt0 += BT) {
+    // WIN: no compare where the wave's 16 rows exist and see all 64 keys:
+    // the tile's last key <= the first row, its first key inside the last
+    // row's window
+    bool need_mask = true;
+    if constexpr (WIN)
+      need_mask = q0 + wave * 16 + 15 >= S ||
+                  kt0 + BT - 1 > q0 + wave * 16 ||
+                  kt0 + window <= q0 + wave * 16 + 15;
     stage_tile<D, true, false>(k, kbase, (int64_t)Hkv * D, kt0, S, k_lds,
                                nullptr);
     stage_tile<D, false, true>(k, kbase, (int64_t)Hkv * D, kt0, S,
@@ -286,17 +347,44 @@ __global__ __launch_bounds__(BLOCK) void attn_bwd_dq_kernel(
       }
       // C layout: row = q (quad*4+r), col = key
       const int kcol = kt0 + ks * 16 + col;
+      if constexpr (WIN) {
+        if (need_mask) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int qrow = q0 + wave * 16 + quad * 4 + r;
-        const int safe = min(qrow, S - 1);
-        const float Lr = lse[lbase + safe];
-        const float Dr = delta[lbase + safe];
-        const bool masked = (qrow >= S) || (kcol >= S) ||
-                            (causal && kcol > qrow) || Lr <= -1e29f;
-        const float p = masked ? 0.f : __expf(s[r] * scale - Lr);
-        const float ds = p * (dp[r] - Dr) * scale;
-        t_lds[wave][quad * 4 + r][ks * 16 + col] = f2bf(ds);
+          for (int r = 0; r < 4; ++r) {
+            const int qrow = q0 + wave * 16 + quad * 4 + r;
+            const int safe = min(qrow, S - 1);
+            const float Lr = lse[lbase + safe];
+            const float Dr = delta[lbase + safe];
+            const bool masked = (qrow >= S) || (kcol >= S) || kcol > qrow ||
+                                kcol + window <= qrow || Lr <= -1e29f;
+            const float p = masked ? 0.f : __expf(s[r] * scale - Lr);
+            const float ds = p * (dp[r] - Dr) * scale;
+            t_lds[wave][quad * 4 + r][ks * 16 + col] = f2bf(ds);
+          }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int qrow = q0 + wave * 16 + quad * 4 + r;
+            const float Lr = lse[lbase + qrow];
+            const float Dr = delta[lbase + qrow];
+            const float p = __expf(s[r] * scale - Lr);
+            const float ds = p * (dp[r] - Dr) * scale;
+            t_lds[wave][quad * 4 + r][ks * 16 + col] = f2bf(ds);
+          }
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int qrow = q0 + wave * 16 + quad * 4 + r;
+          const int safe = min(qrow, S - 1);
+          const float Lr = lse[lbase + safe];
+          const float Dr = delta[lbase + safe];
+          const bool masked = (qrow >= S) || (kcol >= S) ||
+                              (causal && kcol > qrow) || Lr <= -1e29f;
+          const float p = masked ? 0.f : __expf(s[r] * scale - Lr);
+          const float ds = p * (dp[r] - Dr) * scale;
+          t_lds[wave][quad * 4 + r][ks * 16 + col] = f2bf(ds);
+        }
       }
       if (ks & 1) {
         const int kk32 = (ks - 1) * 16;
@@ -334,25 +422,39 @@ __global__ __launch_bounds__(BLOCK) void attn_bwd_dq_kernel(
 
 extern "C" {
 
+// window = 0: the plain kernels. window > 0: the sliding window, causal only
+// (the caller checks), clamped to [1, S]: a window past S hides nothing, and
+// the kernels' `key + window` cannot overflow.
 void tl_attn_bwd(const void* q, const void* k, const void* v,
                  const void* dout, const void* lse, const void* delta,
                  void* dq, void* dk, void* dv, int B, int S, int Hq,
-                 int Hkv, int D, float scale, int causal,
+                 int Hkv, int D, float scale, int causal, int window,
                  hipStream_t stream) {
   dim3 block(BLOCK);
   dim3 gkv((S + BT - 1) / BT, Hkv, B);
   dim3 gq((S + BT - 1) / BT, Hq, B);
+  const int win = window > 0 ? 1 : 0;
+  if (win) {
+    window = max(1, min(window, S));
+    causal = 1;
+  }
 #define L2(KER, GRID, ...)                                                  \
   hipLaunchKernelGGL(KER, GRID, block, 0, stream, (const bf16*)q,           \
                      (const bf16*)k, (const bf16*)v, (const bf16*)dout,     \
                      (const float*)lse, (const float*)delta, __VA_ARGS__,   \
-                     B, S, Hq, Hkv, scale, causal)
-  if (D == 128) {
-    L2((attn_bwd_dkv_kernel<128>), gkv, (bf16*)dk, (bf16*)dv);
-    L2((attn_bwd_dq_kernel<128>), gq, (bf16*)dq);
+                     B, S, Hq, Hkv, scale, causal, window)
+  if (D == 128 && win) {
+    L2((attn_bwd_dkv_kernel<128, 1>), gkv, (bf16*)dk, (bf16*)dv);
+    L2((attn_bwd_dq_kernel<128, 1>), gq, (bf16*)dq);
+  } else if (D == 128) {
+    L2((attn_bwd_dkv_kernel<128, 0>), gkv, (bf16*)dk, (bf16*)dv);
+    L2((attn_bwd_dq_kernel<128, 0>), gq, (bf16*)dq);
+  } else if (D == 64 && win) {
+    L2((attn_bwd_dkv_kernel<64, 1>), gkv, (bf16*)dk, (bf16*)dv);
+    L2((attn_bwd_dq_kernel<64, 1>), gq, (bf16*)dq);
   } else if (D == 64) {
-    L2((attn_bwd_dkv_kernel<64>), gkv, (bf16*)dk, (bf16*)dv);
-    L2((attn_bwd_dq_kernel<64>), gq, (bf16*)dq);
+    L2((attn_bwd_dkv_kernel<64, 0>), gkv, (bf16*)dk, (bf16*)dv);
+    L2((attn_bwd_dq_kernel<64, 0>), gq, (bf16*)dq);
   }
 #undef L2
 }

@@ -221,8 +221,9 @@ void tl_prefill_attn_v3(const void* q, const void* k, const void* v,
                         int64_t v_sb, int64_t v_sh, int64_t v_ss,
                         hipStream_t stream);
 void tl_prefill_attn_win(const void* q, const void* k, const void* v,
-                         void* out, int B, int Sq, int Skv, int q_off,
-                         int Hq, int Hkv, int D, float scale, int window,
+                         void* out, void* lse, int B, int Sq, int Skv,
+                         int q_off, int Hq, int Hkv, int D, float scale,
+                         int window,
                          int64_t k_sb, int64_t k_sh, int64_t k_ss,
                          int64_t v_sb, int64_t v_sh, int64_t v_ss,
                          hipStream_t stream);
@@ -246,9 +247,10 @@ void tl_prefill_attn(const void* q, const void* k, const void* v, void* out,
                      const int64_t* k_strides, const int64_t* v_strides,
                      int use_v3, int window, hipStream_t stream) {
   if (window > 0) {
-    tl_prefill_attn_win(q, k, v, out, B, Sq, Skv, q_off, Hq, Hkv, D, scale,
-                        window, k_strides[0], k_strides[1], k_strides[2],
-                        v_strides[0], v_strides[1], v_strides[2], stream);
+    tl_prefill_attn_win(q, k, v, out, nullptr, B, Sq, Skv, q_off, Hq, Hkv, D,
+                        scale, window, k_strides[0], k_strides[1],
+                        k_strides[2], v_strides[0], v_strides[1],
+                        v_strides[2], stream);
     return;
   }
   tl_prefill_attn_lse(q, k, v, out, nullptr, B, Sq, Skv, q_off, Hq, Hkv, D,

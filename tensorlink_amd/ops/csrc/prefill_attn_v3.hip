@@ -490,25 +490,26 @@ extern "C" void tl_prefill_attn_v3(
 
 // Sliding-window entry: causal, window >= 1 (see the kernel's comment). A
 // window past Skv hides nothing, so it is clamped there and the kernel's
-// `key + window` never overflows.
+// `key + window` never overflows. lse (may be null) receives the logsumexp
+// for the windowed backward.
 extern "C" void tl_prefill_attn_win(
-    const void* q, const void* k, const void* v, void* out, int B, int Sq,
-    int Skv, int q_off, int Hq, int Hkv, int D, float scale, int window,
-    int64_t k_sb, int64_t k_sh, int64_t k_ss, int64_t v_sb, int64_t v_sh,
-    int64_t v_ss, hipStream_t stream) {
+    const void* q, const void* k, const void* v, void* out, void* lse, int B,
+    int Sq, int Skv, int q_off, int Hq, int Hkv, int D, float scale,
+    int window, int64_t k_sb, int64_t k_sh, int64_t k_ss, int64_t v_sb,
+    int64_t v_sh, int64_t v_ss, hipStream_t stream) {
   dim3 grid((Sq + BM - 1) / BM, Hq, B), block(BLOCK);
   window = max(1, min(window, Skv));
   if (D == 128)
     hipLaunchKernelGGL((prefill_attn_v3_kernel<128, 0, 1>), grid, block, 0,
                        stream, (const bf16*)q, (const bf16*)k,
-                       (const bf16*)v, (bf16*)out, (float*)nullptr, B, Sq,
+                       (const bf16*)v, (bf16*)out, (float*)lse, B, Sq,
                        Skv, q_off, Hq, Hkv, scale, 1, k_sb, k_sh, k_ss, v_sb,
                        v_sh, v_ss, (float*)nullptr, (float*)nullptr, 1, 1,
                        window);
   else if (D == 64)
     hipLaunchKernelGGL((prefill_attn_v3_kernel<64, 0, 1>), grid, block, 0,
                        stream, (const bf16*)q, (const bf16*)k,
-                       (const bf16*)v, (bf16*)out, (float*)nullptr, B, Sq,
+                       (const bf16*)v, (bf16*)out, (float*)lse, B, Sq,
                        Skv, q_off, Hq, Hkv, scale, 1, k_sb, k_sh, k_ss, v_sb,
                        v_sh, v_ss, (float*)nullptr, (float*)nullptr, 1, 1,
                        window);
